@@ -19,17 +19,31 @@ starts N child processes of this script itself (RANK/LOCAL_RANK/WORLD_SIZE/MASTE
 before anything here touches the GPU), relays rank 0's line and exits with the first
 failing child's code. `n_gpus` is the number of ranks the process group saw (all_reduce).
 
-At world > 1, after the headline timing, a second leg runs BASELINE config 5: the 4-stage
+At world > 1 with --full, after the headline timing, a second leg runs BASELINE config 5: the 4-stage
 decimating FIR chain domain-partitioned across the ranks (G = 2: stages {1,2}|{3,4};
 G = 4: one stage per rank; 8 ranks = 2 time shards x 4) over domain_adapter_remote, RCCL
 forced when every rank has its own GPU. Its rate, transports and tail parity go into the
 `c5_pipeline` field; a failure there is reported, not fatal to the headline.
 
-Prints ONE JSON line (rank 0) with the roofline of the FIR kernel (HIP events around each
-launch on the partition stream, algorithmic 16 B/sample) and the CPU baseline (the
-scheduler_mt CPU path restated, timed on this host, rank 0 at N=1).
+Prints ONE JSON line (rank 0). A plain run does what the headline needs and no more: set up,
+warm up, time the K steps, write the outputs (--dump-outputs), print the line with the rate,
+`ms_per_step` and the FIR kernel's roofline as the timed run's own HIP events give it (around
+each timed launch on the partition stream, algorithmic 16 B/sample). Everything that takes runs
+or work of its own is behind --full: the tail parity against the oracle, the shader clock, the
+measured copy ceiling, the PMC traffic figure, the exact-fp32 / C5-fused / C2 / C4 / decimator /
+C1 legs, the C5 pipeline leg at world > 1 and the CPU baseline (the scheduler_mt CPU path
+restated, timed on this host, rank 0 at N=1). The switches of those legs (--fp32-leg, --c5,
+--c5-fused, --legs, --no-cpu) choose among them under --full and do nothing without it.
 
-    python bench.py [--gpus N --steps K --warmup W] [--log2n 28] [--algo auto|mfma|direct]
+--dump-outputs DIR writes what the timed run's last step left in the FIR's output ring, as a
+caller of the flowgraph would read it: DIR/y.npy (rank r > 0: y_rank<r>.npy), float32 [rows, 2]
+= (re, im). A last step of up to 2^22 samples is written whole; of a longer one, a fixed seeded
+choice of 4096-sample blocks (the first and the last among them), whose first sample indices
+within the step are in DIR/y_block_start.npy (float64). The input stream is counter-based
+(seed and shard offset fixed), so the same arguments give the same inputs in every run.
+
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full] [--log2n 28]
+                    [--algo auto|mfma|direct]
 """
 from __future__ import annotations
 
@@ -50,6 +64,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level para
 BYTES_PER_SAMPLE = 16  # algorithmic: read x (8 B) + write y (8 B) per output sample
 FLOP_PER_SAMPLE = 508  # 127 taps x 2 (re, im) x FMA
 METRIC = "MSamples/s through 127-tap fir_filter_ccf flowgraph; % HBM roofline at 1/8 GPU"
+DUMP_BLOCK = 4096  # --dump-outputs: samples per block of the sample of a long step
+DUMP_SAMPLES = 1 << 22  # --dump-outputs: complex samples written over all ranks (32 MiB as float32 pairs)
+DUMP_SEED = 0x64756D70
 C5_HALO = 1904  # >= 126*(1+2+4+8) = 1890 input samples, a multiple of the total decimation 16
 
 
@@ -91,6 +108,33 @@ def free_port():
     with socket.socket() as s:  # nothing free below the range: let the kernel choose
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+def dump_block_starts(n, budget):
+    """First sample indices of the 4096-sample blocks --dump-outputs keeps of an n-sample step
+    (n a multiple of 256, n > budget): the first block, the last, and a seeded choice of the
+    block-aligned ones between, `budget` samples in all; sorted, the same in every run."""
+    nb = max(2, budget // DUMP_BLOCK)
+    last = n - DUMP_BLOCK
+    inner = np.arange(1, (last + DUMP_BLOCK - 1) // DUMP_BLOCK, dtype=np.int64)  # k * 4096 < last
+    pick = np.random.default_rng(DUMP_SEED).choice(inner, size=min(nb - 2, inner.size), replace=False)
+    return np.sort(np.concatenate([[0], pick * DUMP_BLOCK, [last]])).astype(np.int64)
+
+
+def dump_outputs(path_dir, fb, n, out_buf_bytes, rank, world):
+    """--dump-outputs: the last step's output from the FIR's output ring (see the module docstring).
+    The ring gives its newest out_buf_bytes / 8 items back; a step longer than that is written from
+    where the ring still holds it."""
+    os.makedirs(path_dir, exist_ok=True)
+    have = min(n, out_buf_bytes // 8)
+    y = fb.tail(have)  # y[i] is sample n - have + i of the step
+    budget = max(DUMP_BLOCK * 2, DUMP_SAMPLES // world)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    if have > budget:
+        starts = dump_block_starts(have, budget)
+        y = np.concatenate([y[s:s + DUMP_BLOCK] for s in starts])
+        np.save(os.path.join(path_dir, "y_block_start%s.npy" % suffix), (starts + (n - have)).astype(np.float64))
+    np.save(os.path.join(path_dir, "y%s.npy" % suffix), np.ascontiguousarray(y).view(np.float32).reshape(-1, 2))
 
 
 def load_pmc_traffic(kernel, samples_per_launch, summary="pmc_fir.json"):
@@ -560,22 +604,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--min-warmup-s", type=float, default=1.0,
                     help="keep warming up (untimed runs) until this long has passed: clocks settle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/y.npy (float32 (re, im) rows; a "
+                         "fixed seeded sample of 4096-sample blocks of a step longer than 2^22 samples)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: tail parity vs the oracle, shader clock, measured copy ceiling, PMC traffic, "
+                         "the fp32 / C5 / C2 / C4 / decimator / C1 legs and the CPU baseline (off: the headline alone)")
     ap.add_argument("--log2n", type=int, default=28)
     ap.add_argument("--algo", default="auto", choices=["auto", "mfma", "mfma_f32", "direct"])
     ap.add_argument("--fp32-leg", choices=["on", "off"], default="on",
-                    help="also time the exact-fp32 matrix form (NSH_FIR_MFMA_F32) on the same flowgraph")
+                    help="under --full: also time the exact-fp32 matrix form (NSH_FIR_MFMA_F32) on the same flowgraph")
     ap.add_argument("--timing-stride", type=int, default=2,
                     help="HIP-event timing on every k-th FIR launch of the timed run (each timed launch costs its "
                          "event packets, ~7 us)")
     ap.add_argument("--out-buf-mib", type=int, default=2048, help="FIR output hip_buffer (default: one launch per 2^28-sample step)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="under --full: skip the CPU baseline")
     ap.add_argument("--cpu-log2n", type=int, default=28, help="CPU baseline sample (default: the full stream)")
-    ap.add_argument("--c5", choices=["auto", "on", "off"], default="auto", help="C5 pipeline leg (auto: at world > 1)")
+    ap.add_argument("--c5", choices=["auto", "on", "off"], default="auto", help="under --full: C5 pipeline leg (auto: at world > 1)")
     ap.add_argument("--c5-fused", choices=["on", "off"], default="on",
-                    help="C5's chain as the fused kernel (k_fir_pfft2<16>) on resident input, every rank")
+                    help="under --full: C5's chain as the fused kernel (k_fir_pfft2<16>) on resident input, every rank")
     ap.add_argument("--c5-fused-log2n", type=int, default=28)
     ap.add_argument("--legs", choices=["auto", "on", "off"], default="auto",
-                    help="the other single-GPU configs beside the headline: C1 (CPU), C2, C4, decimators D=2/4 "
+                    help="under --full: the other single-GPU configs beside the headline: C1 (CPU), C2, C4, decimators D=2/4 "
                          "(auto: at world 1 only -- they are single-GPU configs, and a rank that fails one must "
                          "not leave its peers waiting in the leg's barriers of a multi-GPU run)")
     ap.add_argument("--legs-log2n", type=int, default=28)
@@ -670,20 +720,37 @@ def main():
         elapsed = float(t.item())
     st = fb.stats()
 
-    # parity on the measured path: the last 4096 outputs of the timed run vs the oracle, read
-    # before anything else runs the flowgraph again
-    m = 4096
-    y = fb.tail(m)
-    lo = first + n - m - (taps.size - 1)
-    xw = orc.synth(m + taps.size - 1, lo)
-    y_ref = orc.fir_ccf(xw[taps.size - 1:], taps, hist=xw[: taps.size - 1])
-    ok, err, scale = orc.tol_ok(y, y_ref)
+    # the last step's output, read before anything else runs the flowgraph again
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, fb, n, a.out_buf_mib << 20, rank, world)
 
-    def more():  # untimed: the clock the FIR runs at under the same stream of batches
-        fb.set_batches(24)
-        fb.run()
+    def emit(out, abandoned=False):
+        if dist is not None and not abandoned:
+            dist.barrier()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if abandoned:  # a hung pipeline leg: leave without joining it (the headline is printed)
+            sys.stderr.flush()
+            os._exit(0)
+        if dist is not None:
+            dist.destroy_process_group()
 
-    clock_mhz = leg_clock(more, nsh)
+    ok, err, scale, clock_mhz = True, 0.0, 0.0, None
+    if a.full:
+        # parity on the measured path: the last 4096 outputs of the timed run vs the oracle, likewise
+        # read before the flowgraph runs again
+        m = 4096
+        y = fb.tail(m)
+        lo = first + n - m - (taps.size - 1)
+        xw = orc.synth(m + taps.size - 1, lo)
+        y_ref = orc.fir_ccf(xw[taps.size - 1:], taps, hist=xw[: taps.size - 1])
+        ok, err, scale = orc.tol_ok(y, y_ref)
+
+        def more():  # untimed: the clock the FIR runs at under the same stream of batches
+            fb.set_batches(24)
+            fb.run()
+
+        clock_mhz = leg_clock(more, nsh)
     kms = st["kernel_ms"] - st0["kernel_ms"]
     samples = st["samples"] - st0["samples"]
     algo_used = {1: "direct", 2: "mfma", 5: "mfma_f32"}.get(st["algo"], str(st["algo"]))
@@ -694,7 +761,7 @@ def main():
     avg_launch_ms = kms / timed_launches
     achieved = BYTES_PER_SAMPLE * per_launch_samples / (avg_launch_ms * 1e-3) / 1e9  # GB/s
 
-    if dist is not None:  # every rank's shard tail must pass; report the worst error
+    if dist is not None and a.full:  # every rank's shard tail must pass; report the worst error
         r = torch.tensor([0.0 if ok else 1.0, err], dtype=torch.float64, device=tdev)
         dist.all_reduce(r, op=dist.ReduceOp.MAX)
         ok, err = r[0].item() == 0.0, float(r[1].item())
@@ -746,11 +813,15 @@ def main():
             "flowgraph_achieved": round(BYTES_PER_SAMPLE * n / (step_us * 1e-6) / 1e9, 1),
             "flowgraph_frac": round(BYTES_PER_SAMPLE * n / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
             "overhead_us_per_step": round(step_us - avg_launch_ms * 1e3 * launches_per_run, 2),  # incl. the run's start / drain
-            "clock_mhz": clock_mhz,  # shader clock over an untimed repeat (leg_clock)
         },
-        "parity": {"check": "last 4096 outputs of the timed run's last step vs oracle (double accumulation), every rank",
-                   "max_abs_err": err, "scale": scale, "ok": bool(ok)},
     }
+    if not a.full:  # the headline alone
+        fb.close()
+        emit(out)
+        return
+    out["roofline"]["clock_mhz"] = clock_mhz  # shader clock over an untimed repeat (leg_clock)
+    out["parity"] = {"check": "last 4096 outputs of the timed run's last step vs oracle (double accumulation), every rank",
+                     "max_abs_err": err, "scale": scale, "ok": bool(ok)}
     cp = run_copy_leg(n, barrier, torch, nsh)
     out["roofline"]["copy_measured"] = cp
     out["roofline"]["frac_of_copy"] = round(achieved / cp["GBs"], 4)
@@ -811,15 +882,7 @@ def main():
                       "(4096-item work() calls); %.2f s on %s. fir_work_only_msps: the same block's filter() alone on "
                       "2^24 samples in 4096-sample calls, no scheduler" % (a.cpu_log2n, isa, threads, secs, cpu_model()),
         }
-    if dist is not None and not abandoned:
-        dist.barrier()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if abandoned:  # a hung pipeline leg: leave without joining it (the headline is printed)
-        sys.stderr.flush()
-        os._exit(0)
-    if dist is not None:
-        dist.destroy_process_group()
+    emit(out, abandoned)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,9 @@ import pytest
 from tests.conftest import ROOT
 
 
-ARGS = ["--steps", "3", "--warmup", "1", "--log2n", "22", "--out-buf-mib", "64", "--no-cpu", "--legs-log2n", "22"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--log2n", "22", "--out-buf-mib", "64"]
+# --full: the parity, copy, legs and C5 fields these tests read are behind it
+ARGS = PLAIN + ["--full", "--no-cpu", "--legs-log2n", "22"]
 
 
 def _json_line(stdout):
@@ -66,6 +68,91 @@ def test_c5_layout():
     assert bench.c5_layout(8) == (4, 2)
     assert bench.c5_layout(1) == (1, 1)
     assert bench.c5_layout(6) == (2, 3)
+
+
+def test_dump_block_starts():
+    """--dump-outputs' sample of a long step: the first and the last 4096-sample block and a seeded
+    choice between, disjoint, the budget's worth, the same at every call."""
+    import numpy as np
+    import bench
+
+    n, budget = 1 << 28, 1 << 22
+    s = bench.dump_block_starts(n, budget)
+    assert s.size == budget // bench.DUMP_BLOCK and s[0] == 0 and s[-1] == n - bench.DUMP_BLOCK
+    assert np.all(np.diff(s) >= bench.DUMP_BLOCK)
+    assert np.array_equal(s, bench.dump_block_starts(n, budget))
+    s = bench.dump_block_starts(3 * 4096 + 256, 2 * 4096)  # not a multiple of the block: the last block still ends the step
+    assert s.tolist() == [0, 2 * 4096 + 256]
+    s = bench.dump_block_starts(4 * 4096, 1 << 22)  # fewer blocks than the budget: all of them
+    assert s.tolist() == [0, 4096, 2 * 4096, 3 * 4096]
+
+
+def test_dump_outputs_files(tmp_path):
+    """dump_outputs on a stand-in for the flowgraph's output ring: a short step whole, a long one
+    by blocks with their indices, a ring shorter than the step from where it still holds it;
+    float32 (re, im) rows."""
+    import numpy as np
+    import bench
+
+    class Ring:
+        def __init__(self, n):
+            self.y = (np.arange(n) + 1j * (np.arange(n) % 7)).astype(np.complex64)  # re = the sample's index
+
+        def tail(self, count):
+            return self.y[self.y.size - count:].copy()
+
+    n = 1 << 14
+    bench.dump_outputs(str(tmp_path / "a"), Ring(n), n, n * 8, 0, 1)
+    y = np.load(tmp_path / "a" / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (n, 2) and not (tmp_path / "a" / "y_block_start.npy").exists()
+    assert np.array_equal(y[:, 0], np.arange(n)) and np.array_equal(y[:, 1], np.arange(n) % 7)
+    # a budget below the step (2^22 samples over 2^9 ranks = 8192 = 2 blocks), a rank other than 0
+    n = 1 << 15
+    bench.dump_outputs(str(tmp_path / "b"), Ring(n), n, n * 8, 3, 1 << 9)
+    y = np.load(tmp_path / "b" / "y_rank3.npy")
+    st = np.load(tmp_path / "b" / "y_block_start_rank3.npy")
+    assert st.dtype == np.float64 and st.tolist() == [0.0, float(n - 4096)] and y.shape == (8192, 2)
+    assert np.array_equal(y[:, 0], np.concatenate([np.arange(4096), np.arange(n - 4096, n)]))
+    # the ring holds the step's second half only
+    bench.dump_outputs(str(tmp_path / "c"), Ring(n), n, n * 4, 0, 1 << 9)
+    y = np.load(tmp_path / "c" / "y.npy")
+    st = np.load(tmp_path / "c" / "y_block_start.npy")
+    assert st.tolist() == [float(n // 2), float(n - 4096)]
+    assert np.array_equal(y[:, 0], np.concatenate([np.arange(n // 2, n // 2 + 4096), np.arange(n - 4096, n)]))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(torch_cuda, tmp_path):
+    """A plain run: the headline line without the legs, parity or baselines of --full, --steps timed
+    steps, and --dump-outputs' sample of the last step (2^23 samples: 1024 blocks) equal to the
+    oracle's filter of the stream -- the ring replays x, so the last step's history is x's end."""
+    import numpy as np
+    from oracle import oracle as orc
+    import bench
+
+    n = 1 << 23
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", "23",
+                          "--out-buf-mib", "64", "--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = _json_line(out.stdout)
+    assert d["metric"] == bench.METRIC and d["unit"] == "MSamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["config"]["timed_launches"] >= 1
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    assert 0 < d["roofline"]["frac"] < 1
+    for k in ("parity", "fp32_exact", "c5_fused", "c2", "c4", "decim2", "decim4", "c1", "cpu_baseline", "c5_pipeline"):
+        assert k not in d, k
+    assert "copy_measured" not in d["roofline"] and "clock_mhz" not in d["roofline"]
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["y.npy", "y_block_start.npy"]
+    y = np.load(tmp_path / "y.npy")
+    st = np.load(tmp_path / "y_block_start.npy")
+    assert y.dtype == np.float32 and y.shape == (1 << 22, 2) and st.dtype == np.float64
+    assert np.array_equal(st, bench.dump_block_starts(n, 1 << 22))
+    x = orc.synth(n)
+    ref = orc.fir_ccf(x, bench.firwin(127, 0.2), hist=x[-126:])
+    idx = (st.astype(np.int64)[:, None] + np.arange(bench.DUMP_BLOCK)).ravel()
+    ok, err, scale = orc.tol_ok(np.ascontiguousarray(y).view(np.complex64).ravel(), ref[idx])
+    assert ok, (err, scale)
 
 
 @pytest.mark.gpu
