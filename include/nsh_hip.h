@@ -222,6 +222,37 @@ const char* nsh_fir_cascade_kernel(void* plan); /* "k_fir_pfft2<16>" (D = 16; "k
 int nsh_fir_cascade_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out,
                         int64_t n_out, void* stream);
 
+/* ---- rotator_cc and freq_xlating_fir_filter_ccf (no reference counterpart; GNU Radio semantics) ----
+ * Phase: a frequency is a 64-bit fixed-point phase increment in turns per sample,
+ *   inc = round(frac(t) * 2^64) mod 2^64   (exact from the double t; negative t wraps),
+ * and the phase of absolute stream sample n is (n * inc) mod 2^64 turns in plain uint64 wrap-around
+ * arithmetic: independent of how the stream is cut into calls and of the stream position.
+ *   nsh_phase_inc      host only; refuses a non-finite frequency.
+ *   nsh_rotate_cc      y[i] = x[i] * exp(+j 2 pi phase(first_index + i)); one launch (k_rotate) per
+ *                      call whatever n and the 8-byte pointer alignment; in == out is allowed.
+ *   nsh_fir_xlat_ccf   with inc = phase_inc(-freq_norm), freq_norm = center_freq / samp_rate:
+ *                        y[m] = sum_{k<ntaps} h[k] * (x[m*decim - k] * exp(j 2 pi phase(first_index + m*decim - k)))
+ *                      (= GNU Radio's freq_xlating_fir_filter_ccf: a signal at +center_freq lands at
+ *                      DC), 1 <= decim <= 64, 1 <= ntaps <= 1024, one launch of the fused kernel
+ *                      k_fir_xlat<R,S> (rotate at staging, fp32 direct form, decimate). History as
+ *                      nsh_fir_ccf: hist_in = the ntaps-1 RAW (unrotated) samples before in[0], i.e.
+ *                      stream samples first_index - (ntaps-1) + j mod 2^64 (NULL = zeros); hist_out
+ *                      receives the last ntaps-1 raw samples bit-exactly and must not alias hist_in.
+ *                      Non-finite samples propagate by plain IEEE arithmetic.
+ * Argument errors (NULL pointers, ntaps or decim out of range, a non-finite frequency, aliased
+ * history) are refused before any HIP call; n <= 0 / n_out <= 0 return 0 and launch nothing.
+ * Measured (DESIGN.md section 4.3, 127 taps): the fused kernel is the faster form from decimation 8
+ * upward; at decimation 1, 2 and 4 the staged nsh_rotate_cc -> nsh_fir_ccf(AUTO) is (the MFMA FIR). */
+int nsh_phase_inc(double turns_per_sample, uint64_t* inc);
+int nsh_rotate_cc(const float* in, float* out, int64_t n, uint64_t phase_inc, uint64_t first_index, void* stream);
+int nsh_fir_xlat_plan_create(int dev, const float* taps_host, int ntaps, int decim, double freq_norm, void** plan);
+int nsh_fir_xlat_plan_destroy(void* plan);
+int nsh_fir_xlat_phase_inc(void* plan, uint64_t* inc);       /* = phase_inc(-freq_norm) */
+int nsh_fir_xlat_tile(void* plan);                           /* outputs per workgroup of the chosen instantiation */
+const char* nsh_fir_xlat_kernel(void* plan);                 /* e.g. "k_fir_xlat<4,2>" */
+int nsh_fir_xlat_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out,
+                     int64_t n_out, uint64_t first_index, void* stream);
+
 /* ---- FFT (fft_vcc, 1024-point, unnormalised both ways) ------------------------------
  * frames of 1024 complex samples; inverse=1 computes sum_k X[k] e^{+2 pi i kn/1024}
  * (= 1024 * numpy.fft.ifft). nsh_channelizer1024 fuses fft -> multiply by w[1024]

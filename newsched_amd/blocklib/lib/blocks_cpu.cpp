@@ -1,9 +1,12 @@
 // CPU block implementations (reference blocklib/blocks/lib/*.cpp semantics).
 #include <gnuradio/blocklib/blocks/arith.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
+#include <gnuradio/blocklib/blocks/rotator_cc.hpp>
 
 #include <algorithm>
+#include <complex>
 #include <cstring>
 #include <stdexcept>
 
@@ -223,6 +226,76 @@ work_return_code_t fir_filter_ccf::work(std::vector<block_work_input>& in, std::
     const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
     filter(static_cast<const gr_complex*>(in[0].buffer->read_ptr()), static_cast<gr_complex*>(out[0].buffer->write_ptr()),
            n_out);
+    out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- rotator_cc / freq_xlating_fir_filter_ccf: the 64-bit phase, double sincos -----------------
+bool rotator_cc::start()
+{
+    _index = _first;
+    return block::start();
+}
+
+work_return_code_t rotator_cc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    const int n = out[0].n_items;
+    for (int i = 0; i < n; ++i) {
+        double s, c;
+        phase_sincos((_index + (uint64_t)i) * _inc, s, c);
+        const double re = x[i].real(), im = x[i].imag();
+        y[i] = gr_complex((float)(re * c - im * s), (float)(re * s + im * c));
+    }
+    _index += (uint64_t)n;
+    out[0].n_produced = n;
+    return work_return_code_t::WORK_OK;
+}
+
+freq_xlating_fir_filter_ccf::freq_xlating_fir_filter_ccf(int decim, const std::vector<float>& taps, double center_freq,
+                                                         double samp_rate)
+    : decim_block("freq_xlating_fir_filter_ccf", (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim)
+{
+    if (taps.empty()) throw std::invalid_argument("freq_xlating_fir_filter_ccf: no taps");
+    if (decim < 1) throw std::invalid_argument("freq_xlating_fir_filter_ccf: decimation < 1");
+    if (!(samp_rate > 0)) throw std::invalid_argument("freq_xlating_fir_filter_ccf: samp_rate must be positive");
+    _inc = phase_inc_turns(-(center_freq / samp_rate));
+}
+
+bool freq_xlating_fir_filter_ccf::start()
+{
+    _ext.assign(_taps.size() - 1, gr_complex(0, 0)); // zero history at stream start
+    _index = _first;
+    return block::start();
+}
+
+work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
+    const int L = (int)_taps.size();
+    const size_t n_in = (size_t)n_out * _decim;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    _ext.resize((size_t)(L - 1) + n_in);
+    std::memcpy(_ext.data() + (L - 1), x, n_in * sizeof(gr_complex));
+    // rotate every sample of the window once (the raw history is rotated again with its own phase)
+    std::vector<std::complex<double>> rot(_ext.size());
+    for (size_t i = 0; i < _ext.size(); ++i) {
+        double s, c;
+        phase_sincos((_index + (uint64_t)i - (uint64_t)(L - 1)) * _inc, s, c);
+        const double re = _ext[i].real(), im = _ext[i].imag();
+        rot[i] = std::complex<double>(re * c - im * s, re * s + im * c);
+    }
+    for (int m = 0; m < n_out; ++m) {
+        std::complex<double> acc = 0;
+        const std::complex<double>* w = rot.data() + (size_t)m * _decim + (L - 1);
+        for (int k = 0; k < L; ++k) acc += (double)_taps[k] * w[-k];
+        y[m] = gr_complex((float)acc.real(), (float)acc.imag());
+    }
+    std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
+    _ext.resize((size_t)(L - 1));
+    _index += (uint64_t)n_in;
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;
 }

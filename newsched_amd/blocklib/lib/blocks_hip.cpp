@@ -6,7 +6,9 @@
 #include <gnuradio/blocklib/hip/fft.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_cascade_ccf.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
+#include <gnuradio/blocklib/hip/rotator_cc.hpp>
 #include <gnuradio/blocklib/hip/synth_source.hpp>
 #include <gnuradio/hip_context.hpp>
 
@@ -354,6 +356,91 @@ double fir_filter_cascade_ccf::kernel_ms()
         total += ms;
     }
     return total;
+}
+
+// ---- rotator / frequency-translating FIR ----------------------------------------------
+work_return_code_t rotator_cc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n = out[0].n_items;
+    check(nsh_rotate_cc((const float*)in[0].buffer->read_ptr(), (float*)out[0].buffer->write_ptr(), n, _inc, _index,
+                        current_stream()),
+          "hip::rotator_cc");
+    _index += (uint64_t)n;
+    ++_launches;
+    out[0].n_produced = n;
+    return work_return_code_t::WORK_OK;
+}
+
+freq_xlating_fir_filter_ccf::freq_xlating_fir_filter_ccf(int decim, const std::vector<float>& taps, double center_freq,
+                                                         double samp_rate)
+    : decim_block("freq_xlating_fir_filter_ccf (hip)", (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim)
+{
+    if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: 1 to 1024 taps");
+    if (decim < 1 || decim > 64) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: decimation must be in [1, 64]");
+    if (!(samp_rate > 0)) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: samp_rate must be positive");
+    _freq_norm = center_freq / samp_rate;
+    if (!std::isfinite(_freq_norm)) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: the frequency must be finite");
+}
+
+freq_xlating_fir_filter_ccf::~freq_xlating_fir_filter_ccf() { release(); }
+
+void freq_xlating_fir_filter_ccf::release()
+{
+    if (_plan) nsh_fir_xlat_plan_destroy(_plan);
+    for (auto& h : _hist)
+        if (h) nsh_free(h);
+    _plan = nullptr;
+    _hist[0] = _hist[1] = nullptr;
+}
+
+uint64_t freq_xlating_fir_filter_ccf::phase_inc() const
+{
+    uint64_t inc = 0;
+    if (_plan) nsh_fir_xlat_phase_inc(_plan, &inc);
+    return inc;
+}
+std::string freq_xlating_fir_filter_ccf::kernel() const { return _plan ? nsh_fir_xlat_kernel(_plan) : std::string(); }
+
+bool freq_xlating_fir_filter_ccf::start()
+{
+    const int dev = current_device();
+    if (_plan && dev != _dev) release();
+    const size_t hbytes = std::max<size_t>(_taps.size() - 1, 1) * sizeof(gr_complex);
+    if (!_plan) {
+        _dev = dev;
+        check(nsh_fir_xlat_plan_create(dev, _taps.data(), (int)_taps.size(), _decim, _freq_norm, &_plan),
+              "hip::freq_xlating_fir_filter_ccf plan");
+        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::freq_xlating_fir_filter_ccf history");
+        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::freq_xlating_fir_filter_ccf history");
+    }
+    // the run's first call reads a null history (zeros in the kernel); every call writes its
+    // hist_out in full, so the ping-pong buffers need no clearing
+    _zero_hist = true;
+    if (!_init_hist.empty()) {
+        if (_init_hist.size() != _taps.size() - 1)
+            throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: initial history must have ntaps-1 samples");
+        void* s = current_stream();
+        check(nsh_memcpy_async(_hist[0], _init_hist.data(), hbytes, NSH_H2D, s), "hip::freq_xlating_fir_filter_ccf history load");
+        check(nsh_stream_sync(s), "hip::freq_xlating_fir_filter_ccf history load"); // host vector must outlive the copy
+        _zero_hist = false;
+    }
+    _cur = 0;
+    _index = _first;
+    return block::start();
+}
+
+work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
+    check(nsh_fir_xlat_ccf(_plan, (const float*)in[0].buffer->read_ptr(), _zero_hist ? nullptr : (const float*)_hist[_cur],
+                           (float*)_hist[_cur ^ 1], (float*)out[0].buffer->write_ptr(), n_out, _index, current_stream()),
+          "hip::freq_xlating_fir_filter_ccf");
+    _zero_hist = false;
+    _cur ^= 1;
+    _index += (uint64_t)n_out * (uint64_t)_decim;
+    ++_launches;
+    out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
 }
 
 // ---- FFT ---------------------------------------------------------------------------

@@ -78,6 +78,14 @@ SIGNATURES = {
     "nsh_fir_cascade_hist_len": (_i, [_vp]),
     "nsh_fir_cascade_kernel": (C.c_char_p, [_vp]),
     "nsh_fir_cascade_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_phase_inc": (_i, [C.c_double, C.POINTER(_u64)]),
+    "nsh_rotate_cc": (_i, [_vp, _vp, _i64, _u64, _u64, _vp]),
+    "nsh_fir_xlat_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.c_double, C.POINTER(_vp)]),
+    "nsh_fir_xlat_plan_destroy": (_i, [_vp]),
+    "nsh_fir_xlat_phase_inc": (_i, [_vp, C.POINTER(_u64)]),
+    "nsh_fir_xlat_tile": (_i, [_vp]),
+    "nsh_fir_xlat_kernel": (C.c_char_p, [_vp]),
+    "nsh_fir_xlat_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _vp]),
     "nsh_fft1024_c2c": (_i, [_vp, _vp, _i64, _i, _vp]),
     "nsh_channelizer1024": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
@@ -222,6 +230,58 @@ class FirPlan:
     def close(self):
         if getattr(self, "_h", None):
             lib().nsh_fir_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def phase_inc(turns_per_sample: float) -> int:
+    """round(frac(t) * 2^64) mod 2^64: the 64-bit phase increment of t turns per sample (nsh_phase_inc)."""
+    inc = C.c_uint64(0)
+    check(lib().nsh_phase_inc(float(turns_per_sample), C.byref(inc)), "nsh_phase_inc")
+    return inc.value
+
+
+def rotate_cc(x, y, n: int, inc: int, first_index: int = 0, stream=None):
+    """y[i] = x[i] * exp(2j pi ((first_index + i) * inc mod 2^64) / 2^64); x may be y (nsh_rotate_cc)."""
+    check(lib().nsh_rotate_cc(ptr(x), ptr(y), n, inc & (2**64 - 1), first_index & (2**64 - 1), stream_ptr(stream)),
+          "nsh_rotate_cc")
+
+
+class FirXlatPlan:
+    """Frequency-translating decimating FIR (rotate -> FIR -> decimate in one kernel); see
+    nsh_fir_xlat_ccf. freq_norm = center_freq / samp_rate."""
+
+    def __init__(self, taps, decim: int = 1, freq_norm: float = 0.0, device: int = 0):
+        import numpy as np
+
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+        self.ntaps = int(t.size)
+        self.decim = int(decim)
+        h = C.c_void_p()
+        arr = t.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib().nsh_fir_xlat_plan_create(device, arr, self.ntaps, self.decim, float(freq_norm), C.byref(h)),
+              "nsh_fir_xlat_plan_create")
+        self._h = h
+        inc = C.c_uint64(0)
+        check(lib().nsh_fir_xlat_phase_inc(h, C.byref(inc)), "nsh_fir_xlat_phase_inc")
+        self.inc = inc.value
+        self.tile = lib().nsh_fir_xlat_tile(h)
+        self.kernel = lib().nsh_fir_xlat_kernel(h).decode()
+
+    def __call__(self, x, hist_in, hist_out, y, n_out: int, first_index: int = 0, stream=None):
+        """n_out outputs from n_out * decim inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw samples."""
+        check(lib().nsh_fir_xlat_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
+                                     ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
+                                     first_index & (2**64 - 1), stream_ptr(stream)), "nsh_fir_xlat_ccf")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().nsh_fir_xlat_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):

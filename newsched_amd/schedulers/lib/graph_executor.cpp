@@ -65,6 +65,7 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
         std::vector<block_work_input> win;
         win.reserve(in_ports.size());
         bool ready = true, exhausted = false;
+        std::vector<int> avail; // items readable per input when this iteration looked
         for (auto& p : in_ports) {
             auto buf = _bufman->get_input_buffer(p);
             buffer_info_t ri{};
@@ -80,6 +81,7 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
                 break;
             }
             win.emplace_back(ri.n_items, buf);
+            avail.push_back(ri.n_items);
         }
         if (exhausted) {
             finish(b);
@@ -161,7 +163,18 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
             bool writers_done = !in_ports.empty();
             for (auto& p : in_ports)
                 if (!_bufman->get_input_buffer(p)->writer_done()) writers_done = false;
-            if (writers_done) { // end of stream: leftover input cannot form an output
+            // re-read after seeing the writers done: a writer may have posted its last items between
+            // this iteration's read_info and its done flag (a decimator whose D does not divide the
+            // ring often sits on fewer than D items); the run goes on with them, nothing will notify
+            bool more = false;
+            if (writers_done)
+                for (size_t i = 0; i < in_ports.size(); ++i) {
+                    buffer_info_t ri{};
+                    if (_bufman->get_input_buffer(in_ports[i])->read_info(ri) && ri.n_items > avail[i]) more = true;
+                }
+            if (more) {
+                st[id] = S::READY;
+            } else if (writers_done) { // end of stream: leftover input cannot form an output
                 finish(b);
                 st[id] = S::DONE;
             } else {
