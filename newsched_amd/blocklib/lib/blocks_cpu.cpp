@@ -2,6 +2,7 @@
 #include <gnuradio/blocklib/blocks/arith.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
 #include <gnuradio/blocklib/blocks/rotator_cc.hpp>
 
@@ -296,6 +297,59 @@ work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_inpu
     std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
     _ext.resize((size_t)(L - 1));
     _index += (uint64_t)n_in;
+    out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- pfb_channelizer_ccf: straight from the definition, fp32 ---------------------------------------
+pfb_channelizer_ccf::pfb_channelizer_ccf(int nchans, const std::vector<float>& taps)
+    : decim_block("pfb_channelizer_ccf", (unsigned)(nchans > 0 ? nchans : 1)), _taps(taps), _nchans(nchans)
+{
+    if (taps.empty()) throw std::invalid_argument("pfb_channelizer_ccf: no taps");
+    if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
+        throw std::invalid_argument("pfb_channelizer_ccf: nchans must be a power of two in [2, 64]");
+    _w.resize((size_t)nchans);
+    for (int i = 0; i < nchans; ++i) {
+        const double th = 2.0 * M_PI * (double)i / (double)nchans;
+        _w[i] = gr_complex((float)std::cos(th), (float)std::sin(th));
+    }
+    // the quadrant points exactly
+    _w[0] = gr_complex(1, 0);
+    _w[nchans / 2] = gr_complex(-1, 0);
+    if (nchans >= 4) _w[nchans / 4] = gr_complex(0, 1), _w[3 * nchans / 4] = gr_complex(0, -1);
+}
+
+bool pfb_channelizer_ccf::start()
+{
+    _ext.assign(_taps.size() - 1, gr_complex(0, 0)); // zero history at stream start
+    return block::start();
+}
+
+work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == M * n_out
+    const int L = (int)_taps.size(), M = _nchans;
+    const size_t n_in = (size_t)n_out * M;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    _ext.resize((size_t)(L - 1) + n_in);
+    std::memcpy(_ext.data() + (L - 1), x, n_in * sizeof(gr_complex));
+    for (int m = 0; m < n_out; ++m) {
+        const gr_complex* w = _ext.data() + (size_t)m * M + (L - 1); // x[mM]
+        for (int c = 0; c < M; ++c) {
+            float re = 0.f, im = 0.f;
+            for (int k = 0; k < L; ++k) {
+                const gr_complex e = _w[(size_t)((c * k) & (M - 1))];
+                const float hr = _taps[k] * e.real(), hi = _taps[k] * e.imag();
+                const float xr = w[-k].real(), xi = w[-k].imag();
+                re += hr * xr - hi * xi;
+                im += hr * xi + hi * xr;
+            }
+            y[(size_t)m * M + c] = gr_complex(re, im);
+        }
+    }
+    std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
+    _ext.resize((size_t)(L - 1));
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;
 }

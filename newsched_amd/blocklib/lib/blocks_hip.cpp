@@ -8,6 +8,7 @@
 #include <gnuradio/blocklib/hip/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
+#include <gnuradio/blocklib/hip/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/hip/rotator_cc.hpp>
 #include <gnuradio/blocklib/hip/synth_source.hpp>
 #include <gnuradio/hip_context.hpp>
@@ -438,6 +439,70 @@ work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_inpu
     _zero_hist = false;
     _cur ^= 1;
     _index += (uint64_t)n_out * (uint64_t)_decim;
+    ++_launches;
+    out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- polyphase filterbank channelizer -------------------------------------------------
+pfb_channelizer_ccf::pfb_channelizer_ccf(int nchans, const std::vector<float>& taps)
+    : decim_block("pfb_channelizer_ccf (hip)", (unsigned)(nchans > 0 ? nchans : 1)), _taps(taps), _nchans(nchans)
+{
+    if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::pfb_channelizer_ccf: 1 to 1024 taps");
+    if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
+        throw std::invalid_argument("hip::pfb_channelizer_ccf: nchans must be a power of two in [2, 64]");
+    if ((taps.size() + (size_t)nchans - 1) / (size_t)nchans > 32)
+        throw std::invalid_argument("hip::pfb_channelizer_ccf: at most 32 taps per branch");
+}
+
+pfb_channelizer_ccf::~pfb_channelizer_ccf() { release(); }
+
+void pfb_channelizer_ccf::release()
+{
+    if (_plan) nsh_pfb_plan_destroy(_plan);
+    for (auto& h : _hist)
+        if (h) nsh_free(h);
+    _plan = nullptr;
+    _hist[0] = _hist[1] = nullptr;
+}
+
+std::string pfb_channelizer_ccf::kernel() const { return _plan ? nsh_pfb_kernel(_plan) : std::string(); }
+
+bool pfb_channelizer_ccf::start()
+{
+    const int dev = current_device();
+    if (_plan && dev != _dev) release();
+    const size_t hbytes = std::max<size_t>(_taps.size() - 1, 1) * sizeof(gr_complex);
+    if (!_plan) {
+        _dev = dev;
+        check(nsh_pfb_plan_create(dev, _taps.data(), (int)_taps.size(), _nchans, &_plan), "hip::pfb_channelizer_ccf plan");
+        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::pfb_channelizer_ccf history");
+        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::pfb_channelizer_ccf history");
+    }
+    // the run's first call reads a null history (zeros in the kernel); every call writes its
+    // hist_out in full, so the ping-pong buffers need no clearing
+    _zero_hist = true;
+    if (!_init_hist.empty()) {
+        if (_init_hist.size() != _taps.size() - 1)
+            throw std::invalid_argument("hip::pfb_channelizer_ccf: initial history must have ntaps-1 samples");
+        void* s = current_stream();
+        check(nsh_memcpy_async(_hist[0], _init_hist.data(), hbytes, NSH_H2D, s), "hip::pfb_channelizer_ccf history load");
+        check(nsh_stream_sync(s), "hip::pfb_channelizer_ccf history load"); // host vector must outlive the copy
+        _zero_hist = false;
+    }
+    _cur = 0;
+    return block::start();
+}
+
+work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == M * n_out
+    check(nsh_pfb_channelizer_ccf(_plan, (const float*)in[0].buffer->read_ptr(),
+                                  _zero_hist ? nullptr : (const float*)_hist[_cur], (float*)_hist[_cur ^ 1],
+                                  (float*)out[0].buffer->write_ptr(), n_out, current_stream()),
+          "hip::pfb_channelizer_ccf");
+    _zero_hist = false;
+    _cur ^= 1;
     ++_launches;
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;

@@ -1,0 +1,413 @@
+// libnsh_hip.so: pfb_channelizer_ccf, the critically sampled M-channel polyphase filterbank.
+//
+//   y[m][c] = sum_{k<L} h[k] x[mM - k] exp(+j 2 pi c k / M)         (0 <= c < M, GNU Radio's order)
+//           = sum_{p<M} u_p[m] exp(+j 2 pi c p / M),   u_p[m] = sum_{q<Q} h[p + qM] x[(m-q)M - p]
+//
+// with k = p + qM and Q = ceil(L / M): M branch FIRs of Q real taps, then an unnormalised inverse
+// DFT across the branches. M is a power of two in [2, 64], L <= 1024, Q <= 32.
+//
+//   k_pfb<M>   one launch per call. A 256-thread workgroup makes T = 256 R / M time steps, R = 8
+//              steps per lane: T M = 2048 samples. The (Q-1) M halo it re-reads is 7 M / 2048 of
+//              its tile at Q = 8 (5.5 % at M = 16, 22 % at M = 64), and still the small tile is the
+//              faster one: four- and eight-thousand-sample tiles, with two to three workgroups per
+//              CU instead of five, measured 6 to 49 % slower.
+//     stage    The window of the tile, rows of M samples: row j holds the stream samples of time
+//              step m0 - (Q-1) + j in stream order, x[(m0-Q+1+j) M - (M-1) + c] in column c, so
+//              branch p reads column M-1-p. (T+Q-1) M samples, each read from HBM once per
+//              workgroup with 8-byte non-temporal loads (ring pointers are only 8-byte aligned),
+//              8 pairs per lane in flight as in k_fir_xlat. The stream's first and last tiles read
+//              through virt() (history, zeros). The taps go to LDS as hs[q][p], zero-padded to a
+//              multiple of 4 rows.
+//     FIR      Lane (tg, p) = (tid / M, tid mod M) keeps the R consecutive time steps tg R + t of
+//              branch p. It walks the taps in chunks of 4 and
+//              holds the R + 3 rows the chunk needs in registers; the next chunk moves R - 1 of
+//              them up and reads 4 new rows: R + Qp - 1 ds_read_b64 for R Q MACs (Qp = Q rounded
+//              up to 4). Taps k >= L (the padding up to Qp M) are skipped, never multiplied: a
+//              chunk that holds one takes the path with a per-lane test (0 x NaN would poison a
+//              time step whose window does not hold the sample).
+//     banks    A ds_read_b64 serves lanes 0-31 and 32-63 separately, bank pair = entry mod 32. Lanes
+//              along p read consecutive entries of one row. M >= 32: the 32 lanes of a group read
+//              32 consecutive entries of one row: conflict-free with rows packed, row j at entry
+//              j M. M < 32: a group holds 32 / M time groups tg whose rows are R apart; with rows
+//              packed they would sit R M entries apart, a multiple of 16: on the same banks. The image
+//              therefore leaves one row free after every R: row j at entry (j + (j >> 3)) M, so
+//              neighbouring time groups are 9 M entries apart whatever row of their window they
+//              read, and 9 tg mod (32 / M) takes every value once: 32 different bank pairs.
+//              tests/test_pfb_layout.py recomputes this for every instantiation.
+//     IDFT     Radix-2 decimation in frequency across the M lanes of a time step, log2 M stages of
+//              one lane exchange (xor M/2, M/4, ..., 1) each: the lane without the stage's bit keeps
+//              a + b, the one with it (a_low - a_high) w, w = exp(+j 2 pi (p mod half) / (2 half))
+//              from a table computed in double on the host (exact constants, no runtime sincos).
+//              The last stage's twiddle is 1 and is not multiplied. Lane p ends with channel
+//              bitrev(p).
+//     store    Through a wave-private LDS image (a wave's time steps are its own: no workgroup
+//              barrier after staging), written at [step][bitrev(p)] and read back linearly, so a
+//              wave stores runs of R/2 M contiguous samples, in two rounds of R/2 steps each (half
+//              the image: 10 KiB per workgroup). 16-byte non-temporal stores when out is 16-byte
+//              aligned, the 8-byte path otherwise. The image is padded against the bit-reversed
+//              writes (ds_write_b64: 16 contiguous lanes, bank pair = entry mod 16): M >= 32 one
+//              entry after every 16, M < 32 M entries after every step block of a time group.
+//   Accuracy: fp32 throughout. The DFT mixes the branches, so errors are relative to the largest
+//   channel of a time step, not to each channel. Non-finite samples propagate by IEEE arithmetic: a
+//   NaN in the L-tap window of a time step makes all M channels of that step NaN and no other.
+#include "nsh_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kR = 8;      // consecutive time steps a lane keeps
+constexpr int kQC = 4;     // taps per chunk
+constexpr int kRounds = 2; // store rounds: kR / kRounds time steps each
+constexpr int kStage = 8;  // sample pairs a lane loads before it stores the first
+
+typedef float nf4 __attribute__((ext_vector_type(4)));
+typedef float nf2 __attribute__((ext_vector_type(2)));
+
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+
+template <int M>
+struct geom {
+    static constexpr int LOG2M = ilog2(M);
+    static constexpr int G = kBlock / M;    // time groups
+    static constexpr int T = G * kR;        // time steps per workgroup
+    static constexpr int RH = kR / kRounds; // time steps per store round
+    static constexpr int YW = 64 * RH + 64; // entries of a wave's store image
+    __host__ __device__ static constexpr int row_entry(int j) { return (M < 32 ? j + (j >> 3) : j) * M; }
+    __host__ __device__ static constexpr int ypos(int e)
+    {
+        return M >= 32 ? e + (e >> 4) : e + ((e >> (ilog2(RH) + LOG2M)) << LOG2M);
+    }
+};
+
+// raw stream sample g of this call: the input, the history before it, zeros outside both
+__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g,
+                                       int64_t n_in, int L)
+{
+    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
+    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
+    return make_float2(0.f, 0.f);
+}
+
+__device__ __forceinline__ float2 ld_nt(const float2* p)
+{
+    const nf2 v = __builtin_nontemporal_load(reinterpret_cast<const nf2*>(p));
+    return make_float2(v.x, v.y);
+}
+
+// orders a wave's own LDS accesses (the store image is wave-private: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
+                                                const float2* __restrict__ hist_in,
+                                                float2* __restrict__ hist_out,
+                                                float2* __restrict__ out,
+                                                const float* __restrict__ hp,  // hp[q M + p] = h[p + q M], Qp M floats
+                                                const float2* __restrict__ tw, // tw[s M + p], log2 M - 1 stages
+                                                int L,
+                                                int Q,
+                                                int Qp, // Q rounded up to kQC
+                                                int64_t n_out,
+                                                int vec) // out is 16-byte aligned
+{
+    using g = geom<M>;
+    constexpr int LOG2M = g::LOG2M;
+    extern __shared__ __attribute__((aligned(16))) float2 xs[];
+    const int rows = g::T + Q - 1;
+    float* hs = reinterpret_cast<float*>(xs + g::row_entry(rows));
+    float2* ys = reinterpret_cast<float2*>(hs + Qp * M);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = tid & (M - 1);
+    const int tg = tid >> LOG2M;
+    const int64_t n_in = n_out * M;
+    const int64_t m0 = (int64_t)blockIdx.x * g::T;
+    const int64_t g0 = (m0 - (Q - 1)) * M - (M - 1); // stream sample (of this call) at window position 0
+    const int count = rows * M;
+
+    auto stage = [&](auto load) {
+        for (int i0 = 2 * tid; i0 < count; i0 += 2 * kBlock * kStage) {
+            float2 x0[kStage], x1[kStage];
+#pragma unroll
+            for (int u = 0; u < kStage; ++u) {
+                const int i = i0 + 2 * kBlock * u; // even, count is even: i + 1 < count too
+                x0[u] = i < count ? load(i) : make_float2(0.f, 0.f);
+                x1[u] = i < count ? load(i + 1) : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < kStage; ++u) {
+                const int i = i0 + 2 * kBlock * u;
+                if (i < count) {
+                    const int e = g::row_entry(i >> LOG2M) + (i & (M - 1)); // i and i + 1 share a row
+                    xs[e] = x0[u];
+                    xs[e + 1] = x1[u];
+                }
+            }
+        }
+    };
+    if (g0 >= 0 && g0 + count <= n_in)
+        stage([&](int i) { return ld_nt(in + g0 + i); });
+    else
+        stage([&](int i) { return virt(in, hist_in, g0 + i, n_in, L); });
+    for (int i = tid; i < Qp * M; i += kBlock) hs[i] = hp[i];
+    if (blockIdx.x == 0) { // history for the next call: the L-1 raw samples before in[n_in]
+        for (int j = tid; j < L - 1; j += kBlock) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
+    }
+
+    float2 w[LOG2M > 1 ? LOG2M - 1 : 1];
+#pragma unroll
+    for (int s = 0; s < LOG2M - 1; ++s) w[s] = tw[s * M + p];
+    const int qv = (L - p + M - 1) >> LOG2M; // this branch's taps: q < qv
+    const int qall = L >> LOG2M;             // taps every branch has: q < qall
+    const int col = M - 1 - p;
+    const int ch = (int)(__builtin_bitreverse32((unsigned)p) >> (32 - LOG2M));
+    float2* yw = ys + wave * g::YW;
+    __syncthreads();
+
+    const int trow = tg * kR; // the lane's first time step in the tile
+    auto row = [&](int rho) { return xs[g::row_entry(trow + max(rho, 0)) + col]; };
+
+    float2 acc[kR];
+#pragma unroll
+    for (int t = 0; t < kR; ++t) acc[t] = make_float2(0.f, 0.f);
+    // tap q = q0 + dq of time step t meets row t + Q-1 - q = lo + k, k = t + kQC-1 - dq
+    int lo = Q - kQC;
+    float2 xw[kR + kQC - 1];
+#pragma unroll
+    for (int k = 0; k < kR + kQC - 1; ++k) xw[k] = row(lo + k);
+    for (int q0 = 0; q0 < Qp; q0 += kQC) {
+        float h[kQC];
+#pragma unroll
+        for (int dq = 0; dq < kQC; ++dq) h[dq] = hs[(q0 + dq) * M + p];
+        if (q0 + kQC <= qall) {
+#pragma unroll
+            for (int dq = 0; dq < kQC; ++dq)
+#pragma unroll
+                for (int t = 0; t < kR; ++t) {
+                    acc[t].x = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].x, acc[t].x);
+                    acc[t].y = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].y, acc[t].y);
+                }
+        } else { // the chunk holds taps at or past L: tap by tap, none outside
+#pragma unroll
+            for (int dq = 0; dq < kQC; ++dq) {
+                if (q0 + dq < qv) {
+#pragma unroll
+                    for (int t = 0; t < kR; ++t) {
+                        acc[t].x = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].x, acc[t].x);
+                        acc[t].y = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].y, acc[t].y);
+                    }
+                }
+            }
+        }
+        if (q0 + kQC < Qp) { // slide down by kQC rows
+            lo -= kQC;
+#pragma unroll
+            for (int k = kR - 2; k >= 0; --k) xw[k + kQC] = xw[k];
+#pragma unroll
+            for (int k = 0; k < kQC; ++k) xw[k] = row(lo + k);
+        }
+    }
+
+    // inverse DFT across the M lanes of each time step
+#pragma unroll
+    for (int s = 0; s < LOG2M; ++s) {
+        const int half = M >> (s + 1);
+        const float sgn = (p & half) ? -1.f : 1.f;
+#pragma unroll
+        for (int t = 0; t < kR; ++t) {
+            const float bx = __shfl_xor(acc[t].x, half, 64);
+            const float by = __shfl_xor(acc[t].y, half, 64);
+            const float tx = __builtin_fmaf(acc[t].x, sgn, bx); // a + b, or (the partner's) a - b
+            const float ty = __builtin_fmaf(acc[t].y, sgn, by);
+            if (s < LOG2M - 1) {
+                acc[t].x = __builtin_fmaf(-ty, w[s].y, tx * w[s].x);
+                acc[t].y = __builtin_fmaf(tx, w[s].y, ty * w[s].x);
+            } else {
+                acc[t].x = tx;
+                acc[t].y = ty;
+            }
+        }
+    }
+
+    // the wave's 64 R / M time steps start at mw; its time group tgl holds steps tgl R + t
+    const int tgl = lane >> LOG2M;
+    const int64_t mw = m0 + wave * (64 / M) * kR;
+#pragma unroll
+    for (int rd = 0; rd < kRounds; ++rd) {
+        wave_lds_sync(); // the reads of the round before
+#pragma unroll
+        for (int t = 0; t < g::RH; ++t) yw[g::ypos(((tgl * g::RH + t) << LOG2M) + ch)] = acc[rd * g::RH + t];
+        wave_lds_sync();
+        // image entry e: time group e / (RH M), then RH steps of M channels
+        if (vec) {
+#pragma unroll
+            for (int i = 0; i < g::RH / 2; ++i) {
+                const int e = 2 * (64 * i + lane);
+                const int blk = e >> (ilog2(g::RH) + LOG2M), rest = e & (g::RH * M - 1);
+                const int64_t m = mw + blk * kR + rd * g::RH + (rest >> LOG2M);
+                if (m < n_out) {
+                    const float2 a = yw[g::ypos(e)], b = yw[g::ypos(e) + 1];
+                    const nf4 v = { a.x, a.y, b.x, b.y };
+                    __builtin_nontemporal_store(v, reinterpret_cast<nf4*>(out + m * M + (rest & (M - 1))));
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < g::RH; ++i) {
+                const int e = 64 * i + lane;
+                const int blk = e >> (ilog2(g::RH) + LOG2M), rest = e & (g::RH * M - 1);
+                const int64_t m = mw + blk * kR + rd * g::RH + (rest >> LOG2M);
+                if (m < n_out) {
+                    const float2 a = yw[g::ypos(e)];
+                    const nf2 v = { a.x, a.y };
+                    __builtin_nontemporal_store(v, reinterpret_cast<nf2*>(out + m * M + (rest & (M - 1))));
+                }
+            }
+        }
+    }
+}
+
+struct pfb_plan {
+    int dev = 0;
+    int L = 0, M = 0, Q = 0, Qp = 0, T = 0;
+    size_t lds = 0;
+    float* hp_dev = nullptr;  // Qp M taps, then the twiddles
+    float2* tw_dev = nullptr; // inside hp_dev's allocation
+    const void* fn = nullptr;
+    std::string kernel;
+};
+
+template <int M>
+void setup(pfb_plan* p)
+{
+    using g = geom<M>;
+    p->T = g::T;
+    p->fn = (const void*)k_pfb<M>;
+    p->lds = (size_t)g::row_entry(g::T + p->Q - 1) * sizeof(float2) + (size_t)p->Qp * M * sizeof(float) +
+             (size_t)(kBlock / 64) * g::YW * sizeof(float2);
+}
+
+template <int M>
+void launch_pfb(const pfb_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out, int vec,
+                unsigned grid, hipStream_t s)
+{
+    nsh::launch((k_pfb<M>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out, (const float*)p->hp_dev,
+                (const float2*)p->tw_dev, p->L, p->Q, p->Qp, n_out, vec);
+}
+
+} // namespace
+
+extern "C" {
+
+int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, void** plan)
+{
+    if (!taps_host || !plan) return nsh::fail_msg("nsh_pfb_plan_create: null pointer");
+    if (ntaps < 1 || ntaps > 1024) return nsh::fail_msg("nsh_pfb_plan_create: ntaps must be in [1, 1024]");
+    if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
+        return nsh::fail_msg("nsh_pfb_plan_create: nchans must be a power of two in [2, 64]");
+    const int Q = (ntaps + nchans - 1) / nchans;
+    if (Q > 32) return nsh::fail_msg("nsh_pfb_plan_create: at most 32 taps per branch (ceil(ntaps / nchans) <= 32)");
+    NSH_CK(hipSetDevice(dev));
+    auto* p = new pfb_plan();
+    p->dev = dev;
+    p->L = ntaps;
+    p->M = nchans;
+    p->Q = Q;
+    p->Qp = (Q + kQC - 1) / kQC * kQC;
+    switch (nchans) {
+    case 2: setup<2>(p); break;
+    case 4: setup<4>(p); break;
+    case 8: setup<8>(p); break;
+    case 16: setup<16>(p); break;
+    case 32: setup<32>(p); break;
+    default: setup<64>(p); break;
+    }
+    p->kernel = "k_pfb<" + std::to_string(nchans) + ">";
+    const int M = nchans, stages = ilog2(M);
+    const size_t ntap = (size_t)p->Qp * M;
+    std::vector<float> host(ntap + 2 * (size_t)std::max(stages - 1, 1) * M, 0.f);
+    for (int k = 0; k < ntaps; ++k) host[k] = taps_host[k]; // hp[q M + p] = h[p + q M]
+    for (int s = 0; s < stages - 1; ++s) {
+        const int half = M >> (s + 1);
+        for (int q = 0; q < M; ++q) {
+            double c = 1.0, sn = 0.0;
+            if (q & half) {
+                const int i = q & (half - 1);
+                // the quadrant points exactly, the rest from double
+                const double th = 2.0 * M_PI * (double)i / (double)(2 * half);
+                c = std::cos(th), sn = std::sin(th);
+                if (4 * i == 2 * half) c = 0.0, sn = 1.0;
+            }
+            host[ntap + 2 * ((size_t)s * M + q)] = (float)c;
+            host[ntap + 2 * ((size_t)s * M + q) + 1] = (float)sn;
+        }
+    }
+    // at most 37.5 KiB (M = 64 with 1024 taps)
+    hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
+    if (e == hipSuccess) e = hipMalloc(&p->hp_dev, host.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(p->hp_dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->hp_dev) (void)hipFree(p->hp_dev);
+        delete p;
+        return nsh::fail(e, "nsh_pfb_plan_create");
+    }
+    p->tw_dev = reinterpret_cast<float2*>(p->hp_dev + ntap); // ntap is a multiple of 8 floats
+    *plan = p;
+    return 0;
+}
+
+int nsh_pfb_plan_destroy(void* plan)
+{
+    auto* p = static_cast<pfb_plan*>(plan);
+    if (!p) return 0;
+    if (p->hp_dev) (void)hipFree(p->hp_dev);
+    delete p;
+    return 0;
+}
+
+int nsh_pfb_tile(void* plan) { return plan ? static_cast<pfb_plan*>(plan)->T : 0; }
+const char* nsh_pfb_kernel(void* plan) { return plan ? static_cast<pfb_plan*>(plan)->kernel.c_str() : ""; }
+
+int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n_out,
+                            void* stream)
+{
+    nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
+    // what needs no plan first, so that every refusal can be checked without a device
+    if (hist_in && hist_in == hist_out) return nsh::fail_msg("nsh_pfb_channelizer_ccf: hist_out must not alias hist_in");
+    if (n_out > 0 && (!in || !out)) return nsh::fail_msg("nsh_pfb_channelizer_ccf: null input or output");
+    auto* p = static_cast<pfb_plan*>(plan);
+    if (!p) return nsh::fail_msg("nsh_pfb_channelizer_ccf: null plan");
+    if (n_out <= 0) return 0;
+    if (!hist_out && p->L > 1) return nsh::fail_msg("nsh_pfb_channelizer_ccf: hist_out is required (ntaps-1 samples)");
+    const int64_t grid = (n_out + p->T - 1) / p->T;
+    if (grid > 0x7fffffff || n_out > INT64_MAX / 128) return nsh::fail_msg("nsh_pfb_channelizer_ccf: too many outputs for one call");
+    hipStream_t s = nsh::S(stream);
+    const float2* x = (const float2*)in;
+    const float2* hi = (const float2*)hist_in;
+    float2 *ho = (float2*)hist_out, *y = (float2*)out;
+    const int vec = (uintptr_t)out % 16 == 0 ? 1 : 0;
+    switch (p->M) {
+    case 2: launch_pfb<2>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    case 4: launch_pfb<4>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    case 8: launch_pfb<8>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    case 16: launch_pfb<16>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    case 32: launch_pfb<32>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    default: launch_pfb<64>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
+    }
+    NSH_CK_LAUNCH("nsh_pfb_channelizer_ccf");
+    return 0;
+}
+
+} // extern "C"

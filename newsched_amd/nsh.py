@@ -86,6 +86,11 @@ SIGNATURES = {
     "nsh_fir_xlat_tile": (_i, [_vp]),
     "nsh_fir_xlat_kernel": (C.c_char_p, [_vp]),
     "nsh_fir_xlat_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _vp]),
+    "nsh_pfb_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.POINTER(_vp)]),
+    "nsh_pfb_plan_destroy": (_i, [_vp]),
+    "nsh_pfb_tile": (_i, [_vp]),
+    "nsh_pfb_kernel": (C.c_char_p, [_vp]),
+    "nsh_pfb_channelizer_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "nsh_fft1024_c2c": (_i, [_vp, _vp, _i64, _i, _vp]),
     "nsh_channelizer1024": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
@@ -282,6 +287,42 @@ class FirXlatPlan:
     def close(self):
         if getattr(self, "_h", None):
             lib().nsh_fir_xlat_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PfbPlan:
+    """Critically sampled polyphase filterbank channelizer (nchans branch FIRs and an inverse DFT in
+    one kernel); see nsh_pfb_channelizer_ccf."""
+
+    def __init__(self, taps, nchans: int, device: int = 0):
+        import numpy as np
+
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+        self.ntaps = int(t.size)
+        self.nchans = int(nchans)
+        h = C.c_void_p()
+        arr = t.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib().nsh_pfb_plan_create(device, arr, self.ntaps, self.nchans, C.byref(h)), "nsh_pfb_plan_create")
+        self._h = h
+        self.tile = lib().nsh_pfb_tile(h)
+        self.kernel = lib().nsh_pfb_kernel(h).decode()
+
+    def __call__(self, x, hist_in, hist_out, y, n_out: int, stream=None):
+        """n_out items of nchans channels from n_out * nchans inputs; hist_in (or None = zeros) /
+        hist_out: ntaps-1 raw samples."""
+        check(lib().nsh_pfb_channelizer_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
+                                            ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
+                                            stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().nsh_pfb_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):
