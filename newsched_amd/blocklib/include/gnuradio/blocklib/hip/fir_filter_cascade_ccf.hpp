@@ -14,6 +14,7 @@
 // Tags: propagated as by one decimating block with D = prod D_s (the runtime's rule applied
 // once, graph_executor.cpp), not once per stage.
 #pragma once
+#include <gnuradio/blocklib/hip/fir_stream_state.hpp>
 #include <gnuradio/decim_block.hpp>
 
 #include <utility>
@@ -50,18 +51,11 @@ public:
     uint64_t timed_samples() const { return _timed_samples; } // outputs of the timed launches
 
 private:
-    void release();
     std::vector<stage> _stages;
-    int _dev = -1;
-    void* _plan = nullptr;
-    size_t _hist_len = 0;
-    void* _hist[2] = { nullptr, nullptr };
-    bool _zero_hist = true;
-    int _cur = 0;
+    history_state _state;
     uint64_t _launches = 0;
     bool _timing = false;
-    std::vector<std::pair<void*, void*>> _ev;
-    size_t _ev_used = 0;
+    event_pool _ev;
     uint64_t _timed_samples = 0;
 };
 } // namespace hip

@@ -7,6 +7,7 @@
 // start() on the partition thread (right device and stream) and the history is zeroed on
 // every start() (a fresh stream). Algorithm: nsh_fir_algo (AUTO = MFMA for D = 1).
 #pragma once
+#include <gnuradio/blocklib/hip/fir_stream_state.hpp>
 #include <gnuradio/decim_block.hpp>
 
 namespace gr {
@@ -29,14 +30,14 @@ public:
     int decimation() const { return _decim; }
     const std::vector<float>& taps() const { return _taps; }
     int requested_algo() const { return _algo; } // as given to make() (0 = AUTO)
-    bool has_initial_history() const { return !_init_hist.empty(); }
+    bool has_initial_history() const { return _state.has_initial(); }
     int algo() const; // resolved algorithm (after start())
     std::string kernel() const; // the kernel its work() launches (after start())
     uint64_t launches() const { return _launches; }
 
     // History loaded at start() instead of zeros: the ntaps-1 samples that precede this
     // block's first input (a time shard's halo, regenerated or received by the caller).
-    void set_initial_history(const std::vector<gr_complex>& h) { _init_hist = h; }
+    void set_initial_history(const std::vector<gr_complex>& h) { _state.set_initial(h); }
 
     // Per-launch kernel timing with HIP events on the launch stream (bench/profiling): every
     // `stride`-th launch is timed (its own dispatch records the pair, nsh_time_next_launch).
@@ -54,22 +55,15 @@ public:
     uint64_t timed_samples() const { return _timed_samples; }
 
 private:
-    void release();
-    std::vector<gr_complex> _init_hist;
     bool _timing = false;
     int _stride = 1;
     uint64_t _timed_launches = 0;
-    std::vector<std::pair<void*, void*>> _ev;  // (start, stop) per launch, reused
-    size_t _ev_used = 0;
+    event_pool _ev;
     double _done_ms = 0; // kernel time of the launches folded so far
     uint64_t _timed_samples = 0;
     std::vector<float> _taps;
     int _decim, _algo;
-    int _dev = -1;
-    void* _plan = nullptr;
-    void* _hist[2] = { nullptr, nullptr };
-    bool _zero_hist = true; // the next call reads a null history (zeros): set by start()
-    int _cur = 0;
+    history_state _state;
     uint64_t _launches = 0;
 };
 } // namespace hip

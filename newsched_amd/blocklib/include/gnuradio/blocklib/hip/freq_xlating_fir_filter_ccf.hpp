@@ -12,6 +12,7 @@
 // FIR does the arithmetic this kernel does on the vector ALUs. At D = 16 with 255 taps the two are
 // level (1.04x), and the staged pair is limited to decimation 1, 2, 4, 8 and 16.
 #pragma once
+#include <gnuradio/blocklib/hip/fir_stream_state.hpp>
 #include <gnuradio/decim_block.hpp>
 
 namespace gr {
@@ -40,20 +41,14 @@ public:
     // History loaded at start() instead of zeros: the ntaps-1 RAW samples that precede this block's
     // first input (a time shard's halo); with set_first_index the block reproduces the tail of a
     // longer stream.
-    void set_initial_history(const std::vector<gr_complex>& h) { _init_hist = h; }
+    void set_initial_history(const std::vector<gr_complex>& h) { _state.set_initial(h); }
     void set_first_index(uint64_t n) { _first = n; }
 
 private:
-    void release();
-    std::vector<gr_complex> _init_hist;
     std::vector<float> _taps;
     int _decim;
     double _freq_norm;
-    int _dev = -1;
-    void* _plan = nullptr;
-    void* _hist[2] = { nullptr, nullptr };
-    bool _zero_hist = true; // the next call reads a null history (zeros): set by start()
-    int _cur = 0;
+    history_state _state;
     uint64_t _first = 0, _index = 0;
     uint64_t _launches = 0;
 };

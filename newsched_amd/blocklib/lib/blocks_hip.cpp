@@ -118,66 +118,40 @@ work_return_code_t arith_cc<OP>::work(std::vector<block_work_input>& in, std::ve
 template class arith_cc<0>;
 template class arith_cc<1>;
 
-// ---- FIR ---------------------------------------------------------------------------
-fir_filter_ccf::fir_filter_ccf(const std::vector<float>& taps, int decim, int algo)
-    : decim_block("fir_filter_ccf (hip)", (unsigned)decim), _taps(taps), _decim(decim), _algo(algo)
+// ---- history and timing state of the FIR-family blocks (fir_stream_state.hpp) -------------
+void history_state::release()
 {
-    if (taps.empty()) throw std::invalid_argument("hip::fir_filter_ccf: no taps");
-    if (decim != 1 && decim != 2 && decim != 4 && decim != 8 && decim != 16)
-        throw std::invalid_argument("hip::fir_filter_ccf: decimation must be 1, 2, 4, 8 or 16");
-}
-
-fir_filter_ccf::~fir_filter_ccf() { release(); }
-
-void fir_filter_ccf::release()
-{
-    for (auto& e : _ev) {
-        nsh_event_destroy(e.first);
-        nsh_event_destroy(e.second);
-    }
-    _ev.clear();
-    _ev_used = 0;
-    if (_plan) nsh_fir_plan_destroy(_plan);
+    if (_plan) _destroy(_plan);
     for (auto& h : _hist)
         if (h) nsh_free(h);
     _plan = nullptr;
     _hist[0] = _hist[1] = nullptr;
 }
 
-int fir_filter_ccf::algo() const { return _plan ? nsh_fir_plan_algo(_plan) : _algo; }
-std::string fir_filter_ccf::kernel() const { return _plan ? nsh_fir_plan_kernel(_plan) : std::string(); }
-
-bool fir_filter_ccf::start()
+void history_state::prepare(int dev, const plan_factory& make_plan)
 {
-    const int dev = current_device();
-    if (_plan && dev != _dev) release();
-    const size_t hbytes = std::max<size_t>(_taps.size() - 1, 1) * sizeof(gr_complex);
-    if (!_plan) {
-        _dev = dev;
-        check(nsh_fir_plan_create(dev, _taps.data(), (int)_taps.size(), _decim, _algo, &_plan), "hip::fir_filter_ccf plan");
-        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::fir_filter_ccf history");
-        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::fir_filter_ccf history");
-    }
-    void* s = current_stream();
-    // the run's first call reads a null history (zeros in the kernel): no memset launches per run;
-    // every call writes its hist_out in full, so the ping-pong buffers need no clearing
-    _zero_hist = true;
-    if (!_init_hist.empty()) {
-        if (_init_hist.size() != _taps.size() - 1)
-            throw std::invalid_argument("hip::fir_filter_ccf: initial history must have ntaps-1 samples");
-        check(nsh_memcpy_async(_hist[0], _init_hist.data(), hbytes, NSH_H2D, s), "hip::fir_filter_ccf history load");
-        check(nsh_stream_sync(s), "hip::fir_filter_ccf history load"); // host vector must outlive the copy
-        _zero_hist = false;
-    }
-    _cur = 0;
-    // the events of earlier runs are folded into the total when it is read (kernel_ms), not here:
-    // nothing per run but the two records per launch; a long unread series is folded at 4096
-    if (_ev_used >= 4096) kernel_ms();
-    return block::start();
+    if (on_other_device(dev)) release();
+    if (_plan) return;
+    _dev = dev;
+    _len = make_plan(dev, &_plan);
+    const size_t hbytes = std::max<size_t>(_len, 1) * sizeof(gr_complex);
+    check(nsh_malloc(dev, hbytes, &_hist[0]), (_who + " history").c_str());
+    check(nsh_malloc(dev, hbytes, &_hist[1]), (_who + " history").c_str());
 }
 
-// Kernel timing: the launch records its own start / stop events (nsh_time_next_launch) unless
-// NSH_FIR_TIMING=records asks for the two event records around the call (A/B of the two forms).
+void history_state::begin_run(void* stream)
+{
+    _zero = true;
+    if (!_init.empty()) {
+        if (_init.size() != _len) throw std::invalid_argument(_who + ": initial history must have ntaps-1 samples");
+        const std::string what = _who + " history load";
+        check(nsh_memcpy_async(_hist[0], _init.data(), _len * sizeof(gr_complex), NSH_H2D, stream), what.c_str());
+        check(nsh_stream_sync(stream), what.c_str()); // host vector must outlive the copy
+        _zero = false;
+    }
+    _cur = 0;
+}
+
 static bool timing_by_records()
 {
     static const bool r = [] {
@@ -187,36 +161,98 @@ static bool timing_by_records()
     return r;
 }
 
+void event_pool::release()
+{
+    for (auto& e : _ev) {
+        nsh_event_destroy(e.first);
+        nsh_event_destroy(e.second);
+    }
+    _ev.clear();
+    _used = 0;
+}
+
+void event_pool::arm(void* stream)
+{
+    if (_used == _ev.size()) {
+        std::pair<void*, void*> p{ nullptr, nullptr };
+        check(nsh_event_create(&p.first), _what.c_str());
+        check(nsh_event_create(&p.second), _what.c_str());
+        _ev.push_back(p);
+    }
+    const auto& ev = _ev[_used++];
+    if (timing_by_records())
+        check(nsh_event_record(ev.first, stream), _what.c_str());
+    else // the launch records both events itself (nsh_time_next_launch)
+        check(nsh_time_next_launch(ev.first, ev.second), _what.c_str());
+}
+
+void event_pool::recorded(void* stream)
+{
+    if (timing_by_records()) check(nsh_event_record(_ev[_used - 1].second, stream), _what.c_str());
+}
+
+double event_pool::sum_ms(double total)
+{
+    for (size_t i = 0; i < _used; ++i) {
+        float ms = 0;
+        check(nsh_event_sync(_ev[i].second), _what.c_str());
+        check(nsh_event_elapsed_ms(_ev[i].first, _ev[i].second, &ms), _what.c_str());
+        total += ms;
+    }
+    return total;
+}
+
+// ---- FIR ---------------------------------------------------------------------------
+fir_filter_ccf::fir_filter_ccf(const std::vector<float>& taps, int decim, int algo)
+    : decim_block("fir_filter_ccf (hip)", (unsigned)decim),
+      _ev("hip::fir_filter_ccf"),
+      _taps(taps),
+      _decim(decim),
+      _algo(algo),
+      _state("hip::fir_filter_ccf", nsh_fir_plan_destroy)
+{
+    if (taps.empty()) throw std::invalid_argument("hip::fir_filter_ccf: no taps");
+    if (decim != 1 && decim != 2 && decim != 4 && decim != 8 && decim != 16)
+        throw std::invalid_argument("hip::fir_filter_ccf: decimation must be 1, 2, 4, 8 or 16");
+}
+
+fir_filter_ccf::~fir_filter_ccf() = default;
+
+int fir_filter_ccf::algo() const { return _state.plan() ? nsh_fir_plan_algo(_state.plan()) : _algo; }
+std::string fir_filter_ccf::kernel() const { return _state.plan() ? nsh_fir_plan_kernel(_state.plan()) : std::string(); }
+
+bool fir_filter_ccf::start()
+{
+    const int dev = current_device();
+    if (_state.on_other_device(dev)) _ev.release(); // the events belong to the old device too
+    _state.prepare(dev, [this](int d, void** plan) {
+        check(nsh_fir_plan_create(d, _taps.data(), (int)_taps.size(), _decim, _algo, plan), "hip::fir_filter_ccf plan");
+        return _taps.size() - 1;
+    });
+    _state.begin_run(current_stream());
+    // the events of earlier runs are folded into the total when it is read (kernel_ms), not here:
+    // nothing per run but the two records per launch; a long unread series is folded at 4096
+    if (_ev.pending() >= 4096) kernel_ms();
+    return block::start();
+}
+
 work_return_code_t fir_filter_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
 {
     const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
     void* s = current_stream();
-    std::pair<void*, void*>* ev = nullptr;
-    if (_timing && _launches % (uint64_t)_stride == 0) {
-        if (_ev_used == _ev.size()) {
-            std::pair<void*, void*> p{ nullptr, nullptr };
-            check(nsh_event_create(&p.first), "hip::fir_filter_ccf timing");
-            check(nsh_event_create(&p.second), "hip::fir_filter_ccf timing");
-            _ev.push_back(p);
-        }
-        ev = &_ev[_ev_used++];
-        if (timing_by_records())
-            check(nsh_event_record(ev->first, s), "hip::fir_filter_ccf timing");
-        else // the launch records both events itself (nsh_time_next_launch)
-            check(nsh_time_next_launch(ev->first, ev->second), "hip::fir_filter_ccf timing");
-    }
+    const bool timed = _timing && _launches % (uint64_t)_stride == 0;
+    if (timed) _ev.arm(s);
     NSR_RT(4);
-    check(nsh_fir_ccf(_plan, (const float*)in[0].buffer->read_ptr(), _zero_hist ? nullptr : (const float*)_hist[_cur],
-                      (float*)_hist[_cur ^ 1], (float*)out[0].buffer->write_ptr(), n_out, s),
+    check(nsh_fir_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                      (float*)out[0].buffer->write_ptr(), n_out, s),
           "hip::fir_filter_ccf");
-    _zero_hist = false;
-    if (ev) {
-        if (timing_by_records()) check(nsh_event_record(ev->second, s), "hip::fir_filter_ccf timing");
+    if (timed) {
+        _ev.recorded(s);
         _timed_samples += (uint64_t)n_out;
         ++_timed_launches;
     }
     NSR_RT(5);
-    _cur ^= 1;
+    _state.flip();
     ++_launches;
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;
@@ -224,13 +260,8 @@ work_return_code_t fir_filter_ccf::work(std::vector<block_work_input>& in, std::
 
 double fir_filter_ccf::kernel_ms()
 {
-    for (size_t i = 0; i < _ev_used; ++i) {
-        float ms = 0;
-        check(nsh_event_sync(_ev[i].second), "hip::fir_filter_ccf timing");
-        check(nsh_event_elapsed_ms(_ev[i].first, _ev[i].second, &ms), "hip::fir_filter_ccf timing");
-        _done_ms += ms;
-    }
-    _ev_used = 0; // folded: the events are reused by the next launches
+    _done_ms = _ev.sum_ms(_done_ms);
+    _ev.reuse(); // folded: the events are reused by the next launches
     return _done_ms;
 }
 
@@ -261,38 +292,28 @@ bool fir_filter_cascade_ccf::supported(const std::vector<stage>& st)
 }
 
 fir_filter_cascade_ccf::fir_filter_cascade_ccf(const std::vector<stage>& stages)
-    : decim_block("fir_filter_cascade_ccf (hip)", (unsigned)total_decim(stages)), _stages(stages)
+    : decim_block("fir_filter_cascade_ccf (hip)", (unsigned)total_decim(stages)),
+      _stages(stages),
+      _state("hip::fir_filter_cascade_ccf", nsh_fir_cascade_plan_destroy),
+      _ev("hip::fir_filter_cascade_ccf")
 {
     if (!supported(stages))
         throw std::invalid_argument("hip::fir_filter_cascade_ccf: needs total decimation 8 or 16, finite taps and "
                                     "ceil((len(heq)-1)/D) <= 256");
 }
 
-fir_filter_cascade_ccf::~fir_filter_cascade_ccf() { release(); }
+fir_filter_cascade_ccf::~fir_filter_cascade_ccf() = default;
 
-void fir_filter_cascade_ccf::release()
+std::string fir_filter_cascade_ccf::kernel() const
 {
-    for (auto& e : _ev) {
-        nsh_event_destroy(e.first);
-        nsh_event_destroy(e.second);
-    }
-    _ev.clear();
-    _ev_used = 0;
-    if (_plan) nsh_fir_cascade_plan_destroy(_plan);
-    for (auto& h : _hist)
-        if (h) nsh_free(h);
-    _plan = nullptr;
-    _hist[0] = _hist[1] = nullptr;
+    return _state.plan() ? nsh_fir_cascade_kernel(_state.plan()) : std::string();
 }
-
-std::string fir_filter_cascade_ccf::kernel() const { return _plan ? nsh_fir_cascade_kernel(_plan) : std::string(); }
 
 bool fir_filter_cascade_ccf::start()
 {
     const int dev = current_device();
-    if (_plan && dev != _dev) release();
-    if (!_plan) {
-        _dev = dev;
+    if (_state.on_other_device(dev)) _ev.release(); // the events belong to the old device too
+    _state.prepare(dev, [this](int d, void** plan) {
         std::vector<const float*> tp;
         std::vector<int> nt, dc;
         for (auto& s : _stages) {
@@ -300,16 +321,12 @@ bool fir_filter_cascade_ccf::start()
             nt.push_back((int)s.first.size());
             dc.push_back(s.second);
         }
-        check(nsh_fir_cascade_plan_create(dev, tp.data(), nt.data(), dc.data(), (int)_stages.size(), &_plan),
+        check(nsh_fir_cascade_plan_create(d, tp.data(), nt.data(), dc.data(), (int)_stages.size(), plan),
               "hip::fir_filter_cascade_ccf plan");
-        _hist_len = (size_t)nsh_fir_cascade_hist_len(_plan);
-        const size_t hbytes = std::max<size_t>(_hist_len, 1) * sizeof(gr_complex);
-        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::fir_filter_cascade_ccf history");
-        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::fir_filter_cascade_ccf history");
-    }
-    _zero_hist = true; // a fresh stream: the first call reads a null (zero) history
-    _cur = 0;
-    _ev_used = 0;
+        return (size_t)nsh_fir_cascade_hist_len(*plan);
+    });
+    _state.begin_run(current_stream()); // a fresh stream: the first call reads a null (zero) history
+    _ev.reuse();
     _timed_samples = 0;
     return block::start();
 }
@@ -318,46 +335,21 @@ work_return_code_t fir_filter_cascade_ccf::work(std::vector<block_work_input>& i
 {
     const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
     void* s = current_stream();
-    std::pair<void*, void*>* ev = nullptr;
-    if (_timing) {
-        if (_ev_used == _ev.size()) {
-            std::pair<void*, void*> p{ nullptr, nullptr };
-            check(nsh_event_create(&p.first), "hip::fir_filter_cascade_ccf timing");
-            check(nsh_event_create(&p.second), "hip::fir_filter_cascade_ccf timing");
-            _ev.push_back(p);
-        }
-        ev = &_ev[_ev_used++];
-        if (timing_by_records())
-            check(nsh_event_record(ev->first, s), "hip::fir_filter_cascade_ccf timing");
-        else // the launch records both events itself (nsh_time_next_launch)
-            check(nsh_time_next_launch(ev->first, ev->second), "hip::fir_filter_cascade_ccf timing");
-    }
-    check(nsh_fir_cascade_ccf(_plan, (const float*)in[0].buffer->read_ptr(),
-                              _zero_hist ? nullptr : (const float*)_hist[_cur], (float*)_hist[_cur ^ 1],
+    if (_timing) _ev.arm(s);
+    check(nsh_fir_cascade_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
                               (float*)out[0].buffer->write_ptr(), n_out, s),
           "hip::fir_filter_cascade_ccf");
-    _zero_hist = false;
-    if (ev) {
-        if (timing_by_records()) check(nsh_event_record(ev->second, s), "hip::fir_filter_cascade_ccf timing");
+    if (_timing) {
+        _ev.recorded(s);
         _timed_samples += (uint64_t)n_out;
     }
-    _cur ^= 1;
+    _state.flip();
     ++_launches;
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;
 }
 
-double fir_filter_cascade_ccf::kernel_ms()
-{
-    double total = 0;
-    for (size_t i = 0; i < _ev_used; ++i) {
-        float ms = 0;
-        check(nsh_event_sync(_ev[i].second), "hip::fir_filter_cascade_ccf timing");
-        check(nsh_event_elapsed_ms(_ev[i].first, _ev[i].second, &ms), "hip::fir_filter_cascade_ccf timing");
-        total += ms;
-    }
-    return total;
-}
+double fir_filter_cascade_ccf::kernel_ms() { return _ev.sum_ms(); }
 
 // ---- rotator / frequency-translating FIR ----------------------------------------------
 work_return_code_t rotator_cc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
@@ -374,7 +366,10 @@ work_return_code_t rotator_cc::work(std::vector<block_work_input>& in, std::vect
 
 freq_xlating_fir_filter_ccf::freq_xlating_fir_filter_ccf(int decim, const std::vector<float>& taps, double center_freq,
                                                          double samp_rate)
-    : decim_block("freq_xlating_fir_filter_ccf (hip)", (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim)
+    : decim_block("freq_xlating_fir_filter_ccf (hip)", (unsigned)(decim > 0 ? decim : 1)),
+      _taps(taps),
+      _decim(decim),
+      _state("hip::freq_xlating_fir_filter_ccf", nsh_fir_xlat_plan_destroy)
 {
     if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: 1 to 1024 taps");
     if (decim < 1 || decim > 64) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: decimation must be in [1, 64]");
@@ -383,49 +378,27 @@ freq_xlating_fir_filter_ccf::freq_xlating_fir_filter_ccf(int decim, const std::v
     if (!std::isfinite(_freq_norm)) throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: the frequency must be finite");
 }
 
-freq_xlating_fir_filter_ccf::~freq_xlating_fir_filter_ccf() { release(); }
-
-void freq_xlating_fir_filter_ccf::release()
-{
-    if (_plan) nsh_fir_xlat_plan_destroy(_plan);
-    for (auto& h : _hist)
-        if (h) nsh_free(h);
-    _plan = nullptr;
-    _hist[0] = _hist[1] = nullptr;
-}
+freq_xlating_fir_filter_ccf::~freq_xlating_fir_filter_ccf() = default;
 
 uint64_t freq_xlating_fir_filter_ccf::phase_inc() const
 {
     uint64_t inc = 0;
-    if (_plan) nsh_fir_xlat_phase_inc(_plan, &inc);
+    if (_state.plan()) nsh_fir_xlat_phase_inc(_state.plan(), &inc);
     return inc;
 }
-std::string freq_xlating_fir_filter_ccf::kernel() const { return _plan ? nsh_fir_xlat_kernel(_plan) : std::string(); }
+std::string freq_xlating_fir_filter_ccf::kernel() const
+{
+    return _state.plan() ? nsh_fir_xlat_kernel(_state.plan()) : std::string();
+}
 
 bool freq_xlating_fir_filter_ccf::start()
 {
-    const int dev = current_device();
-    if (_plan && dev != _dev) release();
-    const size_t hbytes = std::max<size_t>(_taps.size() - 1, 1) * sizeof(gr_complex);
-    if (!_plan) {
-        _dev = dev;
-        check(nsh_fir_xlat_plan_create(dev, _taps.data(), (int)_taps.size(), _decim, _freq_norm, &_plan),
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_fir_xlat_plan_create(d, _taps.data(), (int)_taps.size(), _decim, _freq_norm, plan),
               "hip::freq_xlating_fir_filter_ccf plan");
-        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::freq_xlating_fir_filter_ccf history");
-        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::freq_xlating_fir_filter_ccf history");
-    }
-    // the run's first call reads a null history (zeros in the kernel); every call writes its
-    // hist_out in full, so the ping-pong buffers need no clearing
-    _zero_hist = true;
-    if (!_init_hist.empty()) {
-        if (_init_hist.size() != _taps.size() - 1)
-            throw std::invalid_argument("hip::freq_xlating_fir_filter_ccf: initial history must have ntaps-1 samples");
-        void* s = current_stream();
-        check(nsh_memcpy_async(_hist[0], _init_hist.data(), hbytes, NSH_H2D, s), "hip::freq_xlating_fir_filter_ccf history load");
-        check(nsh_stream_sync(s), "hip::freq_xlating_fir_filter_ccf history load"); // host vector must outlive the copy
-        _zero_hist = false;
-    }
-    _cur = 0;
+        return _taps.size() - 1;
+    });
+    _state.begin_run(current_stream());
     _index = _first;
     return block::start();
 }
@@ -433,11 +406,10 @@ bool freq_xlating_fir_filter_ccf::start()
 work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
 {
     const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
-    check(nsh_fir_xlat_ccf(_plan, (const float*)in[0].buffer->read_ptr(), _zero_hist ? nullptr : (const float*)_hist[_cur],
-                           (float*)_hist[_cur ^ 1], (float*)out[0].buffer->write_ptr(), n_out, _index, current_stream()),
+    check(nsh_fir_xlat_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                           (float*)out[0].buffer->write_ptr(), n_out, _index, current_stream()),
           "hip::freq_xlating_fir_filter_ccf");
-    _zero_hist = false;
-    _cur ^= 1;
+    _state.flip();
     _index += (uint64_t)n_out * (uint64_t)_decim;
     ++_launches;
     out[0].n_produced = n_out;
@@ -446,7 +418,10 @@ work_return_code_t freq_xlating_fir_filter_ccf::work(std::vector<block_work_inpu
 
 // ---- polyphase filterbank channelizer -------------------------------------------------
 pfb_channelizer_ccf::pfb_channelizer_ccf(int nchans, const std::vector<float>& taps)
-    : decim_block("pfb_channelizer_ccf (hip)", (unsigned)(nchans > 0 ? nchans : 1)), _taps(taps), _nchans(nchans)
+    : decim_block("pfb_channelizer_ccf (hip)", (unsigned)(nchans > 0 ? nchans : 1)),
+      _taps(taps),
+      _nchans(nchans),
+      _state("hip::pfb_channelizer_ccf", nsh_pfb_plan_destroy)
 {
     if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::pfb_channelizer_ccf: 1 to 1024 taps");
     if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
@@ -455,54 +430,27 @@ pfb_channelizer_ccf::pfb_channelizer_ccf(int nchans, const std::vector<float>& t
         throw std::invalid_argument("hip::pfb_channelizer_ccf: at most 32 taps per branch");
 }
 
-pfb_channelizer_ccf::~pfb_channelizer_ccf() { release(); }
+pfb_channelizer_ccf::~pfb_channelizer_ccf() = default;
 
-void pfb_channelizer_ccf::release()
-{
-    if (_plan) nsh_pfb_plan_destroy(_plan);
-    for (auto& h : _hist)
-        if (h) nsh_free(h);
-    _plan = nullptr;
-    _hist[0] = _hist[1] = nullptr;
-}
-
-std::string pfb_channelizer_ccf::kernel() const { return _plan ? nsh_pfb_kernel(_plan) : std::string(); }
+std::string pfb_channelizer_ccf::kernel() const { return _state.plan() ? nsh_pfb_kernel(_state.plan()) : std::string(); }
 
 bool pfb_channelizer_ccf::start()
 {
-    const int dev = current_device();
-    if (_plan && dev != _dev) release();
-    const size_t hbytes = std::max<size_t>(_taps.size() - 1, 1) * sizeof(gr_complex);
-    if (!_plan) {
-        _dev = dev;
-        check(nsh_pfb_plan_create(dev, _taps.data(), (int)_taps.size(), _nchans, &_plan), "hip::pfb_channelizer_ccf plan");
-        check(nsh_malloc(dev, hbytes, &_hist[0]), "hip::pfb_channelizer_ccf history");
-        check(nsh_malloc(dev, hbytes, &_hist[1]), "hip::pfb_channelizer_ccf history");
-    }
-    // the run's first call reads a null history (zeros in the kernel); every call writes its
-    // hist_out in full, so the ping-pong buffers need no clearing
-    _zero_hist = true;
-    if (!_init_hist.empty()) {
-        if (_init_hist.size() != _taps.size() - 1)
-            throw std::invalid_argument("hip::pfb_channelizer_ccf: initial history must have ntaps-1 samples");
-        void* s = current_stream();
-        check(nsh_memcpy_async(_hist[0], _init_hist.data(), hbytes, NSH_H2D, s), "hip::pfb_channelizer_ccf history load");
-        check(nsh_stream_sync(s), "hip::pfb_channelizer_ccf history load"); // host vector must outlive the copy
-        _zero_hist = false;
-    }
-    _cur = 0;
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_pfb_plan_create(d, _taps.data(), (int)_taps.size(), _nchans, plan), "hip::pfb_channelizer_ccf plan");
+        return _taps.size() - 1;
+    });
+    _state.begin_run(current_stream());
     return block::start();
 }
 
 work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
 {
     const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == M * n_out
-    check(nsh_pfb_channelizer_ccf(_plan, (const float*)in[0].buffer->read_ptr(),
-                                  _zero_hist ? nullptr : (const float*)_hist[_cur], (float*)_hist[_cur ^ 1],
+    check(nsh_pfb_channelizer_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
                                   (float*)out[0].buffer->write_ptr(), n_out, current_stream()),
           "hip::pfb_channelizer_ccf");
-    _zero_hist = false;
-    _cur ^= 1;
+    _state.flip();
     ++_launches;
     out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;

@@ -30,6 +30,13 @@ inline int fail_msg(const char* what)
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// hipFree for a plan's destructor: nothing for a buffer that was never allocated (no HIP call, so a
+// refusal on a machine without a device leaves no HIP error behind)
+inline void dev_free(void* p)
+{
+    if (p) (void)hipFree(p);
+}
+
 // Timing of the next kernel launch on this thread (nsh_time_next_launch): a start / stop event
 // pair that the launch itself records, as part of the kernel's dispatch (hipExtLaunchKernelGGL),
 // instead of two separate event packets around it on the stream. Taken (and cleared) by the first
@@ -159,6 +166,56 @@ __device__ __forceinline__ float2 buf_load_f2(__amdgpu_buffer_rsrc_t r, int byte
 {
     const buf_f2 t = __builtin_bit_cast(buf_f2, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, AUX_LD));
     return make_float2(t.x, t.y);
+}
+
+typedef float nf4 __attribute__((ext_vector_type(4)));
+typedef float nf2 __attribute__((ext_vector_type(2)));
+
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+
+// Raw stream sample g of a call of a kernel with a carried history of L - 1 samples: the input,
+// the history before it, zeros outside both.
+__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g,
+                                       int64_t n_in, int L)
+{
+    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
+    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
+    return make_float2(0.f, 0.f);
+}
+
+__device__ __forceinline__ float2 ld_nt(const float2* p)
+{
+    const nf2 v = __builtin_nontemporal_load(reinterpret_cast<const nf2*>(p));
+    return make_float2(v.x, v.y);
+}
+
+// orders a wave's own LDS accesses (for data that is wave-private: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// Argument checks of the one-kernel stream entry points (nsh_fir_xlat_ccf, nsh_pfb_channelizer_ccf),
+// in their documented order; what needs no plan comes first, so that every refusal can be checked
+// without a device. The plan has L taps and makes T outputs per workgroup. Returns the refusal's
+// code, or 0 with *grid = the workgroups to launch (0: nothing to do).
+template <typename Plan>
+inline int check_stream_call(const char* name, const Plan* p, const float* in, const float* hist_in, const float* hist_out,
+                             const float* out, int64_t n_out, int64_t n_out_max, unsigned* grid)
+{
+    const auto refuse = [name](const char* what) { return fail_msg((std::string(name) + what).c_str()); };
+    *grid = 0;
+    if (hist_in && hist_in == hist_out) return refuse(": hist_out must not alias hist_in");
+    if (n_out > 0 && (!in || !out)) return refuse(": null input or output");
+    if (!p) return refuse(": null plan");
+    if (n_out <= 0) return 0;
+    if (!hist_out && p->L > 1) return refuse(": hist_out is required (ntaps-1 samples)");
+    const int64_t g = (n_out + p->T - 1) / p->T;
+    if (g > 0x7fffffff || n_out > n_out_max) return refuse(": too many outputs for one call");
+    *grid = (unsigned)g;
+    return 0;
 }
 
 } // namespace nsh

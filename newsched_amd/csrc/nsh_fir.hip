@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -31,18 +32,9 @@
 
 namespace {
 
-constexpr int kThreads = 256;
+using nsh::virt;
 
-__device__ __forceinline__ float2 virt(const float2* __restrict__ in,
-                                       const float2* __restrict__ hist,
-                                       int64_t g,
-                                       int64_t n_in,
-                                       int L)
-{
-    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
-    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
-    return make_float2(0.f, 0.f);
-}
+constexpr int kThreads = 256;
 
 template <int D, int R>
 __global__ __launch_bounds__(kThreads) void k_fir_direct(const float2* __restrict__ in,
@@ -147,6 +139,17 @@ int run_direct(const nsh_fir_plan* p, const float2* in, const float2* hin, float
 
 } // namespace
 
+nsh_fir_plan::~nsh_fir_plan()
+{
+    nsh::dev_free(taps_dev);
+    nsh::dev_free(frag12_dev);
+    nsh::dev_free(tf32_dev);
+    nsh::dev_free(tf32q_dev);
+    nsh::dev_free(fragd8_dev);
+    if (casc) nsh_fir_cascade_plan_destroy(casc);
+    for (auto& q : xq) nsh::dev_free(q.d);
+}
+
 extern "C" {
 
 int nsh_fir_plan_create(int dev, const float* taps_host, int ntaps, int decim, int algo, void** plan)
@@ -155,7 +158,7 @@ int nsh_fir_plan_create(int dev, const float* taps_host, int ntaps, int decim, i
     if (decim != 1 && decim != 2 && decim != 4 && decim != 8 && decim != 16)
         return nsh::fail_msg("nsh_fir_plan_create: decimation must be 1, 2, 4, 8 or 16");
     NSH_CK(hipSetDevice(dev));
-    auto* p = new nsh_fir_plan();
+    auto p = std::make_unique<nsh_fir_plan>(); // frees what it holds on every refusal below
     p->dev = dev;
     if (hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) p->n_cu = 256;
     p->L = ntaps;
@@ -166,71 +169,43 @@ int nsh_fir_plan_create(int dev, const float* taps_host, int ntaps, int decim, i
     std::copy(taps_host, taps_host + ntaps, padded.begin());
     hipError_t e = hipMalloc(&p->taps_dev, p->Lp * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->taps_dev, padded.data(), p->Lp * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        delete p;
-        return nsh::fail(e, "nsh_fir_plan_create: taps upload");
-    }
-    if (algo < NSH_FIR_AUTO || algo > NSH_FIR_PFFT) {
-        (void)hipFree(p->taps_dev);
-        delete p;
-        return nsh::fail_msg("nsh_fir_plan_create: unknown algorithm");
-    }
-    if (algo == NSH_FIR_MFMA16 || algo == NSH_FIR_MFMA_BF16X3) {
-        (void)hipFree(p->taps_dev);
-        delete p;
+    if (e != hipSuccess) return nsh::fail(e, "nsh_fir_plan_create: taps upload");
+    if (algo < NSH_FIR_AUTO || algo > NSH_FIR_PFFT) return nsh::fail_msg("nsh_fir_plan_create: unknown algorithm");
+    if (algo == NSH_FIR_MFMA16 || algo == NSH_FIR_MFMA_BF16X3)
         return nsh::fail_msg("nsh_fir_plan_create: the MFMA16 / MFMA_BF16X3 kernels were retired (use NSH_FIR_MFMA or "
                              "NSH_FIR_MFMA_F32)");
-    }
     int resolved = algo;
     // decim 8 and 16: the polyphase-FFT kernel (k_fir_pfft; 2x the direct form at 127 taps, 5x at
     // 511) when the filter fits its 256 overlap rows, else the direct form (decim 8 only)
     const bool pfft_ok = (decim == 8 || decim == 16) && (ntaps - 1 + decim - 1) / decim <= 256 &&
                          std::all_of(taps_host, taps_host + ntaps, [](float v) { return std::isfinite(v); });
     if (algo == NSH_FIR_AUTO)
-        resolved = pfft_ok ? NSH_FIR_PFFT : (nsh_fir_mfma_supported(p) ? NSH_FIR_MFMA : NSH_FIR_DIRECT);
-    if ((resolved == NSH_FIR_PFFT && !pfft_ok) || (decim == 16 && resolved != NSH_FIR_PFFT)) {
-        (void)hipFree(p->taps_dev);
-        delete p;
+        resolved = pfft_ok ? NSH_FIR_PFFT : (nsh_fir_mfma_supported(p.get()) ? NSH_FIR_MFMA : NSH_FIR_DIRECT);
+    if ((resolved == NSH_FIR_PFFT && !pfft_ok) || (decim == 16 && resolved != NSH_FIR_PFFT))
         return nsh::fail_msg("nsh_fir_plan_create: PFFT needs decim 8 or 16, finite taps and ntaps <= 256 decim + 1; "
                              "decim 16 needs PFFT");
-    }
     if (resolved == NSH_FIR_PFFT) {
         const float* tp[1] = { taps_host };
         const int nt[1] = { ntaps }, dc[1] = { decim };
         const int rc = nsh_fir_cascade_plan_create(dev, tp, nt, dc, 1, &p->casc);
-        if (rc) {
-            (void)hipFree(p->taps_dev);
-            delete p;
-            return rc;
-        }
+        if (rc) return rc;
         p->algo = NSH_FIR_PFFT;
         p->kernel = nsh_fir_cascade_kernel(p->casc);
-        *plan = p;
+        *plan = p.release();
         return 0;
     }
     if (resolved == NSH_FIR_MFMA_F32) {
-        const int rc = nsh_fir_f32_supported(p) ? nsh_fir_f32_prepare(p)
-                                                : nsh::fail_msg("nsh_fir_plan_create: MFMA_F32 form needs decim 1, finite taps and ntaps <= 257");
-        if (rc) {
-            if (p->tf32_dev) (void)hipFree(p->tf32_dev);
-            (void)hipFree(p->taps_dev);
-            delete p;
-            return rc;
-        }
+        const int rc = nsh_fir_f32_supported(p.get())
+                           ? nsh_fir_f32_prepare(p.get())
+                           : nsh::fail_msg("nsh_fir_plan_create: MFMA_F32 form needs decim 1, finite taps and ntaps <= 257");
+        if (rc) return rc;
     }
     if (resolved == NSH_FIR_MFMA) {
-        if (!nsh_fir_mfma_supported(p)) {
-            (void)hipFree(p->taps_dev);
-            delete p;
+        if (!nsh_fir_mfma_supported(p.get()))
             return nsh::fail_msg("nsh_fir_plan_create: MFMA form needs finite taps and decim 1 with ntaps <= 161, "
                                  "decim 2 with ntaps <= 160 or decim 4 with ntaps <= 320");
-        }
-        const int rc = nsh_fir_mfma_prepare(p);
-        if (rc) {
-            (void)hipFree(p->taps_dev);
-            delete p;
-            return rc;
-        }
+        const int rc = nsh_fir_mfma_prepare(p.get());
+        if (rc) return rc;
     }
     p->algo = resolved;
     if (resolved == NSH_FIR_DIRECT) {
@@ -239,24 +214,15 @@ int nsh_fir_plan_create(int dev, const float* taps_host, int ntaps, int decim, i
     } else if (resolved == NSH_FIR_MFMA_F32) {
         // named by nsh_fir_f32_prepare
     } else {
-        p->kernel = nsh_fir_mfma_kernel_name(p);
+        p->kernel = nsh_fir_mfma_kernel_name(p.get());
     }
-    *plan = p;
+    *plan = p.release();
     return 0;
 }
 
 int nsh_fir_plan_destroy(void* plan)
 {
-    auto* p = static_cast<nsh_fir_plan*>(plan);
-    if (!p) return 0;
-    if (p->taps_dev) (void)hipFree(p->taps_dev);
-    if (p->frag12_dev) (void)hipFree(p->frag12_dev);
-    if (p->tf32_dev) (void)hipFree(p->tf32_dev);
-    if (p->tf32q_dev) (void)hipFree(p->tf32q_dev);
-    if (p->fragd8_dev) (void)hipFree(p->fragd8_dev);
-    if (p->casc) nsh_fir_cascade_plan_destroy(p->casc);
-    for (auto& q : p->xq) (void)hipFree(q.d);
-    delete p;
+    delete static_cast<nsh_fir_plan*>(plan);
     return 0;
 }
 

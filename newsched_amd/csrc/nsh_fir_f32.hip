@@ -39,8 +39,8 @@
 namespace {
 
 using nsh_f32t::f32x4;
-typedef float nf4 __attribute__((ext_vector_type(4)));
 using nsh::AUX_NT;
+using nsh::nf4;
 
 template <int QF>
 struct geomf32 : nsh_f32t::geom<QF - 1, QF> {

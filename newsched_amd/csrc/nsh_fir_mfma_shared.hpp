@@ -32,24 +32,17 @@ using nsh::AUX_NT;
 using nsh::buf_load_f4;
 using nsh::buf_store_f2;
 using nsh::chunk_rsrc;
+using nsh::nf2;
+using nsh::nf4;
 using nsh::u32x2;
+using nsh::virt;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef float nf4 __attribute__((ext_vector_type(4)));
-typedef float nf2 __attribute__((ext_vector_type(2)));
 
 constexpr int TILE = 512;   // outputs per wave per chunk
 constexpr int QMAX = 6;     // L <= 161
-
-__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g, int64_t n_in, int L)
-{
-    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
-    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
-    return make_float2(0.f, 0.f);
-}
-
 
 
 // ---- fp16x2: per-chunk scaled split, three products (default for decim 1) -------------------

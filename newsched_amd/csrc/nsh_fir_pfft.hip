@@ -51,6 +51,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -72,6 +73,7 @@ using nsh::cmulw;
 using nsh::dft4;
 using nsh::dft8;
 using nsh::rot;
+using nsh::virt;
 
 #ifndef NSH_PFFT_ASM_CMUL
 #define NSH_PFFT_ASM_CMUL 1
@@ -235,14 +237,6 @@ __device__ __forceinline__ void fft512_multi(cf (&v)[PW][8], const img_bases& ib
         dft8<false>(v[i]); // pass 3 (Ns = 64) -> X[j + 64 r], kept in registers
     }
     __builtin_amdgcn_wave_barrier(); // the images are rewritten next
-}
-
-__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g,
-                                       int64_t n_in, int L)
-{
-    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
-    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
-    return make_float2(0.f, 0.f);
 }
 
 __device__ __forceinline__ unsigned absbits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
@@ -1089,6 +1083,17 @@ struct nsh_fir_casc_plan {
     int sd[MAX_STAGES] = {};
     int n1 = 0;
     std::string kernel;
+
+    nsh_fir_casc_plan() = default;
+    nsh_fir_casc_plan(const nsh_fir_casc_plan&) = delete;
+    nsh_fir_casc_plan& operator=(const nsh_fir_casc_plan&) = delete;
+    ~nsh_fir_casc_plan()
+    {
+        nsh::dev_free(F);
+        nsh::dev_free(tw);
+        nsh::dev_free(heq);
+        nsh::dev_free(stap);
+    }
 };
 
 #if NSH_PFFT_TRACE
@@ -1128,7 +1133,7 @@ int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const in
     const int L = (int)heq.size();
     const int Q = (L - 1 + D - 1) / D;
     if (Q > M / 2) return nsh::fail_msg("nsh_fir_cascade_plan_create: composite filter longer than 256 output rows");
-    auto* p = new nsh_fir_casc_plan();
+    auto p = std::make_unique<nsh_fir_casc_plan>();
     p->D = D;
     p->L = L;
     p->Q = Q;
@@ -1188,10 +1193,8 @@ int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const in
     if (D == 16) {
         const char* fe = std::getenv("NSH_PFFT_FORM");
         p->form = fe && *fe ? std::atoi(fe) : NSH_PFFT_FORM16;
-        if (p->form != 1 && p->form != 2) {
-            delete p;
+        if (p->form != 1 && p->form != 2)
             return nsh::fail_msg("nsh_fir_cascade_plan_create: NSH_PFFT_FORM must be 1 or 2");
-        }
     }
     if (e == hipSuccess) {
         if (p->form == 2)
@@ -1201,29 +1204,16 @@ int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const in
         else
             e = set_lds_attr((const void*)k_fir_pfft<8, PW8>, lds_bytes<8>(), p->dev);
     }
-    if (e != hipSuccess) {
-        if (p->F) (void)hipFree(p->F);
-        if (p->tw) (void)hipFree(p->tw);
-        if (p->heq) (void)hipFree(p->heq);
-        if (p->stap) (void)hipFree(p->stap);
-        delete p;
-        return nsh::fail(e, "nsh_fir_cascade_plan_create");
-    }
+    if (e != hipSuccess) return nsh::fail(e, "nsh_fir_cascade_plan_create");
     p->kernel = p->form == 2 ? std::string("k_fir_pfft2<16>")
                              : "k_fir_pfft<" + std::to_string(D) + "," + std::to_string(D == 16 ? PW16 : PW8) + ">";
-    *plan = p;
+    *plan = p.release();
     return 0;
 }
 
 int nsh_fir_cascade_plan_destroy(void* plan)
 {
-    auto* p = static_cast<nsh_fir_casc_plan*>(plan);
-    if (!p) return 0;
-    if (p->F) (void)hipFree(p->F);
-    if (p->tw) (void)hipFree(p->tw);
-    if (p->heq) (void)hipFree(p->heq);
-    if (p->stap) (void)hipFree(p->stap);
-    delete p;
+    delete static_cast<nsh_fir_casc_plan*>(plan);
     return 0;
 }
 

@@ -46,6 +46,11 @@ struct nsh_fir_plan {
     int walk_wgpc = 2;    // k_fir_mfma13: workgroups per CU (the lockstep row is 8 x n_cu x this / 8 wide)
     int n_cu = 0;         // the device's CU count, queried once (0 = not yet)
     std::string kernel;   // the kernel nsh_fir_ccf launches (rocprof name without namespace)
+
+    nsh_fir_plan() = default;
+    nsh_fir_plan(const nsh_fir_plan&) = delete;
+    nsh_fir_plan& operator=(const nsh_fir_plan&) = delete;
+    ~nsh_fir_plan(); // frees every device buffer above, the queues and casc (nsh_fir.hip)
 };
 
 std::string nsh_fir_mfma_kernel_name(const nsh_fir_plan* p);

@@ -54,6 +54,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -65,10 +66,12 @@ constexpr int kQC = 4;     // taps per chunk
 constexpr int kRounds = 2; // store rounds: kR / kRounds time steps each
 constexpr int kStage = 8;  // sample pairs a lane loads before it stores the first
 
-typedef float nf4 __attribute__((ext_vector_type(4)));
-typedef float nf2 __attribute__((ext_vector_type(2)));
-
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+using nsh::ilog2;
+using nsh::ld_nt;
+using nsh::nf2;
+using nsh::nf4;
+using nsh::virt;
+using nsh::wave_lds_sync;
 
 template <int M>
 struct geom {
@@ -83,29 +86,6 @@ struct geom {
         return M >= 32 ? e + (e >> 4) : e + ((e >> (ilog2(RH) + LOG2M)) << LOG2M);
     }
 };
-
-// raw stream sample g of this call: the input, the history before it, zeros outside both
-__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g,
-                                       int64_t n_in, int L)
-{
-    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
-    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
-    return make_float2(0.f, 0.f);
-}
-
-__device__ __forceinline__ float2 ld_nt(const float2* p)
-{
-    const nf2 v = __builtin_nontemporal_load(reinterpret_cast<const nf2*>(p));
-    return make_float2(v.x, v.y);
-}
-
-// orders a wave's own LDS accesses (the store image is wave-private: no workgroup barrier)
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 template <int M>
 __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
@@ -285,19 +265,17 @@ struct pfb_plan {
     size_t lds = 0;
     float* hp_dev = nullptr;  // Qp M taps, then the twiddles
     float2* tw_dev = nullptr; // inside hp_dev's allocation
+    // the instantiation, chosen once at plan creation (setup): the kernel and its launcher
     const void* fn = nullptr;
+    void (*launch)(const pfb_plan*, const float2*, const float2*, float2*, float2*, int64_t, int, unsigned,
+                   hipStream_t) = nullptr;
     std::string kernel;
-};
 
-template <int M>
-void setup(pfb_plan* p)
-{
-    using g = geom<M>;
-    p->T = g::T;
-    p->fn = (const void*)k_pfb<M>;
-    p->lds = (size_t)g::row_entry(g::T + p->Q - 1) * sizeof(float2) + (size_t)p->Qp * M * sizeof(float) +
-             (size_t)(kBlock / 64) * g::YW * sizeof(float2);
-}
+    pfb_plan() = default;
+    pfb_plan(const pfb_plan&) = delete;
+    pfb_plan& operator=(const pfb_plan&) = delete;
+    ~pfb_plan() { nsh::dev_free(hp_dev); }
+};
 
 template <int M>
 void launch_pfb(const pfb_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out, int vec,
@@ -305,6 +283,17 @@ void launch_pfb(const pfb_plan* p, const float2* in, const float2* hin, float2* 
 {
     nsh::launch((k_pfb<M>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out, (const float*)p->hp_dev,
                 (const float2*)p->tw_dev, p->L, p->Q, p->Qp, n_out, vec);
+}
+
+template <int M>
+void setup(pfb_plan* p)
+{
+    using g = geom<M>;
+    p->T = g::T;
+    p->fn = (const void*)k_pfb<M>;
+    p->launch = launch_pfb<M>;
+    p->lds = (size_t)g::row_entry(g::T + p->Q - 1) * sizeof(float2) + (size_t)p->Qp * M * sizeof(float) +
+             (size_t)(kBlock / 64) * g::YW * sizeof(float2);
 }
 
 } // namespace
@@ -320,19 +309,19 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
     const int Q = (ntaps + nchans - 1) / nchans;
     if (Q > 32) return nsh::fail_msg("nsh_pfb_plan_create: at most 32 taps per branch (ceil(ntaps / nchans) <= 32)");
     NSH_CK(hipSetDevice(dev));
-    auto* p = new pfb_plan();
+    auto p = std::make_unique<pfb_plan>();
     p->dev = dev;
     p->L = ntaps;
     p->M = nchans;
     p->Q = Q;
     p->Qp = (Q + kQC - 1) / kQC * kQC;
     switch (nchans) {
-    case 2: setup<2>(p); break;
-    case 4: setup<4>(p); break;
-    case 8: setup<8>(p); break;
-    case 16: setup<16>(p); break;
-    case 32: setup<32>(p); break;
-    default: setup<64>(p); break;
+    case 2: setup<2>(p.get()); break;
+    case 4: setup<4>(p.get()); break;
+    case 8: setup<8>(p.get()); break;
+    case 16: setup<16>(p.get()); break;
+    case 32: setup<32>(p.get()); break;
+    default: setup<64>(p.get()); break;
     }
     p->kernel = "k_pfb<" + std::to_string(nchans) + ">";
     const int M = nchans, stages = ilog2(M);
@@ -358,22 +347,15 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
     hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
     if (e == hipSuccess) e = hipMalloc(&p->hp_dev, host.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->hp_dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (p->hp_dev) (void)hipFree(p->hp_dev);
-        delete p;
-        return nsh::fail(e, "nsh_pfb_plan_create");
-    }
+    if (e != hipSuccess) return nsh::fail(e, "nsh_pfb_plan_create");
     p->tw_dev = reinterpret_cast<float2*>(p->hp_dev + ntap); // ntap is a multiple of 8 floats
-    *plan = p;
+    *plan = p.release();
     return 0;
 }
 
 int nsh_pfb_plan_destroy(void* plan)
 {
-    auto* p = static_cast<pfb_plan*>(plan);
-    if (!p) return 0;
-    if (p->hp_dev) (void)hipFree(p->hp_dev);
-    delete p;
+    delete static_cast<pfb_plan*>(plan);
     return 0;
 }
 
@@ -384,28 +366,14 @@ int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, f
                             void* stream)
 {
     nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
-    // what needs no plan first, so that every refusal can be checked without a device
-    if (hist_in && hist_in == hist_out) return nsh::fail_msg("nsh_pfb_channelizer_ccf: hist_out must not alias hist_in");
-    if (n_out > 0 && (!in || !out)) return nsh::fail_msg("nsh_pfb_channelizer_ccf: null input or output");
     auto* p = static_cast<pfb_plan*>(plan);
-    if (!p) return nsh::fail_msg("nsh_pfb_channelizer_ccf: null plan");
-    if (n_out <= 0) return 0;
-    if (!hist_out && p->L > 1) return nsh::fail_msg("nsh_pfb_channelizer_ccf: hist_out is required (ntaps-1 samples)");
-    const int64_t grid = (n_out + p->T - 1) / p->T;
-    if (grid > 0x7fffffff || n_out > INT64_MAX / 128) return nsh::fail_msg("nsh_pfb_channelizer_ccf: too many outputs for one call");
-    hipStream_t s = nsh::S(stream);
-    const float2* x = (const float2*)in;
-    const float2* hi = (const float2*)hist_in;
-    float2 *ho = (float2*)hist_out, *y = (float2*)out;
+    unsigned grid = 0;
+    const int rc =
+        nsh::check_stream_call("nsh_pfb_channelizer_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 128, &grid);
+    if (rc || !grid) return rc;
     const int vec = (uintptr_t)out % 16 == 0 ? 1 : 0;
-    switch (p->M) {
-    case 2: launch_pfb<2>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    case 4: launch_pfb<4>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    case 8: launch_pfb<8>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    case 16: launch_pfb<16>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    case 32: launch_pfb<32>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    default: launch_pfb<64>(p, x, hi, ho, y, n_out, vec, (unsigned)grid, s); break;
-    }
+    p->launch(p, (const float2*)in, (const float2*)hist_in, (float2*)hist_out, (float2*)out, n_out, vec, grid,
+              nsh::S(stream));
     NSH_CK_LAUNCH("nsh_pfb_channelizer_ccf");
     return 0;
 }

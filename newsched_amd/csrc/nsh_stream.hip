@@ -26,7 +26,7 @@ namespace {
 constexpr int kBlock = 256;
 
 // Native clang vectors (the nontemporal builtins reject HIP_vector_type wrappers).
-typedef float nf4 __attribute__((ext_vector_type(4)));
+using nsh::nf4;
 typedef unsigned nu4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_nt(const float4* p)
 {

@@ -37,6 +37,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -46,7 +47,8 @@ constexpr int kBlock = 256;
 constexpr int kUnroll = 4;
 constexpr int kStage = 8; // sample pairs a lane loads before it rotates the first (k_fir_xlat's staging)
 
-typedef float nf4 __attribute__((ext_vector_type(4)));
+using nsh::nf4;
+using nsh::virt;
 
 // exp(j 2 pi p / 2^64) from the top 32 bits of p
 __device__ __forceinline__ float2 phasor(uint64_t p)
@@ -105,15 +107,6 @@ __global__ __launch_bounds__(kBlock) void k_rotate(const float2* in, float2* out
         if (threadIdx.x == 0 && head) rotate_one(in, out, 0, inc, first);
         if (threadIdx.x == 1 && ((n - head) & 1)) rotate_one(in, out, n - 1, inc, first);
     }
-}
-
-// raw stream sample g of this call: the input, the history before it, zeros outside both
-__device__ __forceinline__ float2 virt(const float2* __restrict__ in, const float2* __restrict__ hist, int64_t g,
-                                       int64_t n_in, int L)
-{
-    if (g >= 0) return g < n_in ? in[g] : make_float2(0.f, 0.f);
-    if (g >= -(int64_t)(L - 1)) return hist ? hist[g + (L - 1)] : make_float2(0.f, 0.f); // null: zeros
-    return make_float2(0.f, 0.f);
 }
 
 template <int R, int S>
@@ -255,8 +248,16 @@ struct xlat_plan {
     uint64_t inc = 0;
     float2 step = { 1.f, 0.f };
     float* grev_dev = nullptr;
+    // the instantiation, chosen once at plan creation (pick): the kernel and its launcher
     const void* fn = nullptr;
+    void (*launch)(const xlat_plan*, const float2*, const float2*, float2*, float2*, int64_t, uint64_t, unsigned,
+                   hipStream_t) = nullptr;
     std::string kernel;
+
+    xlat_plan() = default;
+    xlat_plan(const xlat_plan&) = delete;
+    xlat_plan& operator=(const xlat_plan&) = delete;
+    ~xlat_plan() { nsh::dev_free(grev_dev); }
 };
 
 int phase_inc(double t, uint64_t* inc)
@@ -281,6 +282,14 @@ void launch_xlat(const xlat_plan* p, const float2* in, const float2* hin, float2
 {
     nsh::launch((k_fir_xlat<R, S>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out,
                 (const float*)p->grev_dev, p->L, p->D, p->a, p->Lc, n_out, p->inc, first, p->step);
+}
+
+template <int R, int S>
+void pick(xlat_plan* p)
+{
+    p->R = R, p->S = S;
+    p->fn = (const void*)k_fir_xlat<R, S>;
+    p->launch = launch_xlat<R, S>;
 }
 
 } // namespace
@@ -318,23 +327,22 @@ int nsh_fir_xlat_plan_create(int dev, const float* taps_host, int ntaps, int dec
     uint64_t inc = 0;
     if (phase_inc(-freq_norm, &inc)) return nsh::fail_msg("nsh_fir_xlat_plan_create: the frequency must be finite");
     NSH_CK(hipSetDevice(dev));
-    auto* p = new xlat_plan();
+    auto p = std::make_unique<xlat_plan>();
     p->dev = dev;
     p->L = ntaps;
     p->D = decim;
     p->inc = inc;
     p->step = step_phasor(inc);
-    if (decim <= 4) {
-        p->R = 8, p->S = 1, p->fn = (const void*)k_fir_xlat<8, 1>;
-    } else if (decim <= 8) {
-        p->R = 4, p->S = 1, p->fn = (const void*)k_fir_xlat<4, 1>;
-    } else if (decim <= 16) {
-        p->R = 4, p->S = 2, p->fn = (const void*)k_fir_xlat<4, 2>;
-    } else if (decim <= 32) {
-        p->R = 4, p->S = 4, p->fn = (const void*)k_fir_xlat<4, 4>;
-    } else {
-        p->R = 2, p->S = 4, p->fn = (const void*)k_fir_xlat<2, 4>;
-    }
+    if (decim <= 4)
+        pick<8, 1>(p.get());
+    else if (decim <= 8)
+        pick<4, 1>(p.get());
+    else if (decim <= 16)
+        pick<4, 2>(p.get());
+    else if (decim <= 32)
+        pick<4, 4>(p.get());
+    else
+        pick<2, 4>(p.get());
     p->T = kBlock * p->R / p->S;
     p->kernel = "k_fir_xlat<" + std::to_string(p->R) + "," + std::to_string(p->S) + ">";
     const int RD = p->R * decim;
@@ -349,21 +357,14 @@ int nsh_fir_xlat_plan_create(int dev, const float* taps_host, int ntaps, int dec
     for (int q = 0; q < ntaps; ++q) grev[q] = taps_host[ntaps - 1 - q];
     if (e == hipSuccess) e = hipMalloc(&p->grev_dev, grev.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->grev_dev, grev.data(), grev.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (p->grev_dev) (void)hipFree(p->grev_dev);
-        delete p;
-        return nsh::fail(e, "nsh_fir_xlat_plan_create");
-    }
-    *plan = p;
+    if (e != hipSuccess) return nsh::fail(e, "nsh_fir_xlat_plan_create");
+    *plan = p.release();
     return 0;
 }
 
 int nsh_fir_xlat_plan_destroy(void* plan)
 {
-    auto* p = static_cast<xlat_plan*>(plan);
-    if (!p) return 0;
-    if (p->grev_dev) (void)hipFree(p->grev_dev);
-    delete p;
+    delete static_cast<xlat_plan*>(plan);
     return 0;
 }
 
@@ -381,29 +382,12 @@ int nsh_fir_xlat_ccf(void* plan, const float* in, const float* hist_in, float* h
                      uint64_t first_index, void* stream)
 {
     nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
-    // what needs no plan first, so that every refusal can be checked without a device
-    if (hist_in && hist_in == hist_out) return nsh::fail_msg("nsh_fir_xlat_ccf: hist_out must not alias hist_in");
-    if (n_out > 0 && (!in || !out)) return nsh::fail_msg("nsh_fir_xlat_ccf: null input or output");
     auto* p = static_cast<xlat_plan*>(plan);
-    if (!p) return nsh::fail_msg("nsh_fir_xlat_ccf: null plan");
-    if (n_out <= 0) return 0;
-    if (!hist_out && p->L > 1) return nsh::fail_msg("nsh_fir_xlat_ccf: hist_out is required (ntaps-1 samples)");
-    const int64_t grid = (n_out + p->T - 1) / p->T;
-    if (grid > 0x7fffffff || n_out > INT64_MAX / 64) return nsh::fail_msg("nsh_fir_xlat_ccf: too many outputs for one call");
-    hipStream_t s = nsh::S(stream);
-    const float2* x = (const float2*)in;
-    const float2* hi = (const float2*)hist_in;
-    float2 *ho = (float2*)hist_out, *y = (float2*)out;
-    if (p->R == 8)
-        launch_xlat<8, 1>(p, x, hi, ho, y, n_out, first_index, (unsigned)grid, s);
-    else if (p->R == 4 && p->S == 1)
-        launch_xlat<4, 1>(p, x, hi, ho, y, n_out, first_index, (unsigned)grid, s);
-    else if (p->R == 4 && p->S == 2)
-        launch_xlat<4, 2>(p, x, hi, ho, y, n_out, first_index, (unsigned)grid, s);
-    else if (p->R == 4)
-        launch_xlat<4, 4>(p, x, hi, ho, y, n_out, first_index, (unsigned)grid, s);
-    else
-        launch_xlat<2, 4>(p, x, hi, ho, y, n_out, first_index, (unsigned)grid, s);
+    unsigned grid = 0;
+    const int rc = nsh::check_stream_call("nsh_fir_xlat_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 64, &grid);
+    if (rc || !grid) return rc;
+    p->launch(p, (const float2*)in, (const float2*)hist_in, (float2*)hist_out, (float2*)out, n_out, first_index, grid,
+              nsh::S(stream));
     NSH_CK_LAUNCH("nsh_fir_xlat_ccf");
     return 0;
 }

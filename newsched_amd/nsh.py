@@ -211,17 +211,42 @@ def channelizer1024(x, y, w, nframes: int, stream=None):
           "nsh_channelizer1024")
 
 
-class FirPlan:
-    """Device-resident FIR plan (taps uploaded/split once); see nsh_fir_ccf."""
+class _Plan:
+    """A native plan handle (_h) with the C function that destroys it (_destroy, by name)."""
 
-    def __init__(self, taps, decim: int = 1, algo: int = FIR_AUTO, device: int = 0):
+    _destroy = ""
+    _h = None
+
+    @staticmethod
+    def _taps_arg(taps):
+        """taps as a contiguous float32 array (kept by the caller across the call) and its POINTER(c_float)."""
         import numpy as np
 
         t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+        return t, t.ctypes.data_as(C.POINTER(C.c_float))
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FirPlan(_Plan):
+    """Device-resident FIR plan (taps uploaded/split once); see nsh_fir_ccf."""
+
+    _destroy = "nsh_fir_plan_destroy"
+
+    def __init__(self, taps, decim: int = 1, algo: int = FIR_AUTO, device: int = 0):
+        t, arr = self._taps_arg(taps)
         self.ntaps = int(t.size)
         self.decim = int(decim)
         h = C.c_void_p()
-        arr = t.ctypes.data_as(C.POINTER(C.c_float))
         check(lib().nsh_fir_plan_create(device, arr, self.ntaps, self.decim, algo, C.byref(h)),
               "nsh_fir_plan_create")
         self._h = h
@@ -231,17 +256,6 @@ class FirPlan:
     def __call__(self, x, hist_in, hist_out, y, n_out: int, stream=None):
         check(lib().nsh_fir_ccf(self._h, ptr(x), ptr(hist_in), ptr(hist_out), ptr(y), n_out,
                                 stream_ptr(stream)), "nsh_fir_ccf")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().nsh_fir_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def phase_inc(turns_per_sample: float) -> int:
@@ -257,18 +271,17 @@ def rotate_cc(x, y, n: int, inc: int, first_index: int = 0, stream=None):
           "nsh_rotate_cc")
 
 
-class FirXlatPlan:
+class FirXlatPlan(_Plan):
     """Frequency-translating decimating FIR (rotate -> FIR -> decimate in one kernel); see
     nsh_fir_xlat_ccf. freq_norm = center_freq / samp_rate."""
 
-    def __init__(self, taps, decim: int = 1, freq_norm: float = 0.0, device: int = 0):
-        import numpy as np
+    _destroy = "nsh_fir_xlat_plan_destroy"
 
-        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+    def __init__(self, taps, decim: int = 1, freq_norm: float = 0.0, device: int = 0):
+        t, arr = self._taps_arg(taps)
         self.ntaps = int(t.size)
         self.decim = int(decim)
         h = C.c_void_p()
-        arr = t.ctypes.data_as(C.POINTER(C.c_float))
         check(lib().nsh_fir_xlat_plan_create(device, arr, self.ntaps, self.decim, float(freq_norm), C.byref(h)),
               "nsh_fir_xlat_plan_create")
         self._h = h
@@ -284,30 +297,18 @@ class FirXlatPlan:
                                      ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
                                      first_index & (2**64 - 1), stream_ptr(stream)), "nsh_fir_xlat_ccf")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().nsh_fir_xlat_plan_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PfbPlan:
+class PfbPlan(_Plan):
     """Critically sampled polyphase filterbank channelizer (nchans branch FIRs and an inverse DFT in
     one kernel); see nsh_pfb_channelizer_ccf."""
 
-    def __init__(self, taps, nchans: int, device: int = 0):
-        import numpy as np
+    _destroy = "nsh_pfb_plan_destroy"
 
-        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+    def __init__(self, taps, nchans: int, device: int = 0):
+        t, arr = self._taps_arg(taps)
         self.ntaps = int(t.size)
         self.nchans = int(nchans)
         h = C.c_void_p()
-        arr = t.ctypes.data_as(C.POINTER(C.c_float))
         check(lib().nsh_pfb_plan_create(device, arr, self.ntaps, self.nchans, C.byref(h)), "nsh_pfb_plan_create")
         self._h = h
         self.tile = lib().nsh_pfb_tile(h)
@@ -320,28 +321,17 @@ class PfbPlan:
                                             ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
                                             stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().nsh_pfb_plan_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FirCascadePlan:
+class FirCascadePlan(_Plan):
     """A chain of fir_filter_ccf(taps_s, decim_s) stages as one pass; see nsh_fir_cascade_ccf."""
 
-    def __init__(self, stages, device: int = 0):
-        import numpy as np
+    _destroy = "nsh_fir_cascade_plan_destroy"
 
-        self._taps = [np.ascontiguousarray(np.asarray(t, dtype=np.float32)) for t, _ in stages]
-        n = len(self._taps)
-        tp = (C.POINTER(C.c_float) * n)(*[t.ctypes.data_as(C.POINTER(C.c_float)) for t in self._taps])
-        nt = (C.c_int * n)(*[int(t.size) for t in self._taps])
+    def __init__(self, stages, device: int = 0):
+        taps = [self._taps_arg(t) for t, _ in stages]
+        n = len(taps)
+        tp = (C.POINTER(C.c_float) * n)(*[arr for _, arr in taps])
+        nt = (C.c_int * n)(*[int(t.size) for t, _ in taps])
         dc = (C.c_int * n)(*[int(d) for _, d in stages])
         h = C.c_void_p()
         check(lib().nsh_fir_cascade_plan_create(device, tp, nt, dc, n, C.byref(h)), "nsh_fir_cascade_plan_create")
@@ -356,14 +346,3 @@ class FirCascadePlan:
                                         ptr(hist_in) if hist_in is not None else None,
                                         ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
                                         stream_ptr(stream)), "nsh_fir_cascade_ccf")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().nsh_fir_cascade_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
