@@ -291,7 +291,19 @@ int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, f
 /* ---- FFT (fft_vcc, 1024-point, unnormalised both ways) ------------------------------
  * frames of 1024 complex samples; inverse=1 computes sum_k X[k] e^{+2 pi i kn/1024}
  * (= 1024 * numpy.fft.ifft). nsh_channelizer1024 fuses fft -> multiply by w[1024]
- * (complex, device) -> ifft in one pass over HBM. */
+ * (complex, device) -> ifft in one pass over HBM, bit-identical to nsh_fft1024_c2c ->
+ * nsh_mul_const_vcc(vlen 1024) -> nsh_fft1024_c2c(inverse) (the scheduler's fusion relies on it).
+ * in, out and w need only 8-byte alignment (one complex sample; results are bit-identical to the
+ * 16-byte aligned call); in and out must not alias. Exactly nframes * 1024 samples are read and
+ * written for any nframes >= 1.
+ * Frames are independent: a frame's output depends on that frame's samples alone, bit for bit,
+ * whatever the batch size and its place in it; a non-finite sample makes all 1024 outputs of its
+ * own frame non-finite (NaN in both parts for a nan+nanj sample) and touches no other frame. Which
+ * part turns NaN and which inf is not specified.
+ * Scaling the input by a power of two scales the output by it exactly, as long as nothing
+ * overflows or turns subnormal (the growth is at most 1024 sqrt(2) per transform).
+ * Argument errors (NULL in / out / w, in == out) are refused before any HIP call; nframes <= 0
+ * returns 0 and launches nothing, whatever the pointers. */
 int nsh_fft1024_c2c(const float* in, float* out, int64_t nframes, int inverse, void* stream);
 int nsh_channelizer1024(const float* in, float* out, const float* w, int64_t nframes, void* stream);
 

@@ -107,3 +107,86 @@ def test_add_mul_cc_oracle():
     np.testing.assert_allclose(orc.add_cc(a, b), a + b, rtol=0, atol=0)
     p = orc.mul_cc(a, b)
     np.testing.assert_allclose(p, (a.astype(np.complex128) * b).astype(np.complex64), rtol=1e-6, atol=1e-7)
+
+
+# ---- what tests/test_gpu_fft.py and tests/test_gpu_stream_edges.py lean on -----------------------
+def _rand_w(seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(-1, 1, 1024) + 1j * rng.uniform(-1, 1, 1024)).astype(np.complex64)
+
+
+def test_fft_oracle_impulse_basis_is_the_dft_matrix():
+    """Frame p = unit impulse at p: the forward output is exp(-2j pi p k / 1024), the inverse its
+    conjugate. The oracle computes in double and rounds once to fp32, so each part is within half
+    an ulp of a value in [0.5, 1] (2^-25) and each element within 2^-24 = 6e-8 (measured: 3.7e-8)."""
+    eye = np.eye(1024, dtype=np.complex64)
+    pk = (np.arange(1024)[:, None] * np.arange(1024)[None, :]) % 1024  # exact phase index
+    dft = np.exp(-2j * np.pi * pk / 1024)
+    for inverse, want in ((False, dft), (True, dft.conj())):
+        got = orc.fft1024(eye.ravel(), inverse=inverse).reshape(1024, 1024)
+        err = float(np.abs(got.astype(np.complex128) - want).max())
+        assert err <= 2.0 ** -24, (inverse, err)
+
+
+def test_channelizer_oracle_impulse_basis_is_the_circulant():
+    """An impulse at p through fft -> w -> ifft is 1024 ifft(w) rotated by p (numpy, double)."""
+    w = _rand_w(1)
+    h = 1024 * np.fft.ifft(w.astype(np.complex128))
+    idx = (np.arange(1024)[None, :] - np.arange(1024)[:, None]) % 1024  # row p, column n: h[n - p]
+    want = h[idx]
+    got = orc.channelizer1024(np.eye(1024, dtype=np.complex64).ravel(), w).reshape(1024, 1024)
+    err = float(np.abs(got.astype(np.complex128) - want).max())
+    assert err <= 2.0 ** -23 * float(np.abs(h).max()), err  # one fp32 rounding of the output
+
+
+def test_fft_oracle_nonfinite_stays_in_its_frame():
+    """One bad sample in frame 1 of 3: frames 0 and 2 keep their bits, every output of frame 1 is
+    non-finite in at least one part, and NaN in both for a nan+nanj sample."""
+    x = orc.synth(3 * 1024, 21)
+    w = _rand_w(2)
+    ops = (lambda v: orc.fft1024(v), lambda v: orc.fft1024(v, inverse=True), lambda v: orc.channelizer1024(v, w))
+    nan, inf = float("nan"), float("inf")
+    for bad in (complex(nan, nan), complex(inf, 0.0), complex(0.25, -inf), complex(nan, 0.5)):
+        xb = x.copy()
+        xb[1024 + 77] = bad
+        for op in ops:
+            y, yb = op(x), op(xb)
+            for f in (0, 2):
+                np.testing.assert_array_equal(yb[1024 * f:1024 * (f + 1)].view(np.uint32),
+                                              y[1024 * f:1024 * (f + 1)].view(np.uint32))
+            mid = yb[1024:2048]
+            assert np.all(~np.isfinite(mid.real) | ~np.isfinite(mid.imag))
+            if np.isnan(bad.real) and np.isnan(bad.imag):
+                assert np.all(np.isnan(mid.real) & np.isnan(mid.imag))
+
+
+def test_fft_oracle_power_of_two_scaling_is_exact():
+    """fft(s x) == s fft(x) bit for bit for s = 2^-60, 2^60, 2^100 (nothing under- or overflows:
+    samples are multiples of 2^-23 in [-1, 1), the growth is at most 1024 sqrt(2))."""
+    x = orc.synth(5 * 1024, 22)
+    w = _rand_w(3)
+    ops = (lambda v: orc.fft1024(v), lambda v: orc.fft1024(v, inverse=True), lambda v: orc.channelizer1024(v, w))
+    for e in (-60, 60, 100):
+        s = np.float32(2.0 ** e)
+        for op in ops:
+            np.testing.assert_array_equal(op(x * s).view(np.uint32), (op(x) * s).view(np.uint32))
+
+
+def test_synth_oracle_wraps_at_2_64():
+    """g = 2 (first + i) mod 2^64: the oracle against the numpy splitmix64 of oracle/gen_golden.py on
+    indices reduced in Python integers, at first_index values around 2^31, 2^32, 2^40 and the wrap."""
+    from oracle import gen_golden as gg
+
+    def restated(n, first, seed):
+        g = np.array([(2 * (first + i // 2) + (i & 1)) % 2 ** 64 for i in range(2 * n)], dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            z = gg.splitmix64(g ^ np.uint64(seed))
+        u = (z >> np.uint64(40)).astype(np.int64).astype(np.float32) * np.float32(2.0 ** -23) - np.float32(1.0)
+        return (u[0::2] + 1j * u[1::2]).astype(np.complex64)
+
+    for first in (2 ** 31 - 3, 2 ** 32 - 3, 2 ** 40 + 1, 2 ** 63 - 2, 2 ** 64 - 5):
+        np.testing.assert_array_equal(orc.synth(4097, first), restated(4097, first, orc.SEED))
+    np.testing.assert_array_equal(orc.synth(4097, 2 ** 64 - 5, seed=0x1234567), restated(4097, 2 ** 64 - 5, 0x1234567))
+    np.testing.assert_array_equal(orc.synth(8), gg.synth(8))
+    assert orc.synth(2, 2 ** 63 - 1)[1] == orc.synth(1, 0)[0]  # 2 * 2^63 wraps to 0
+    np.testing.assert_array_equal(orc.synth(100, 2 ** 63 + 5), orc.synth(100, 5))
