@@ -3,6 +3,7 @@
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
+#include <gnuradio/blocklib/blocks/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
 #include <gnuradio/blocklib/blocks/rotator_cc.hpp>
 
@@ -351,6 +352,49 @@ work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, 
     std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
     _ext.resize((size_t)(L - 1));
     out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- rational_resampler_ccf: straight from the definition, fp32 -------------------------------------
+rational_resampler_ccf::rational_resampler_ccf(int interp, int decim, const std::vector<float>& taps)
+    : resamp_block("rational_resampler_ccf", (unsigned)(interp > 0 ? interp : 1), (unsigned)(decim > 0 ? decim : 1)),
+      _taps(taps),
+      _interp(interp),
+      _decim(decim)
+{
+    if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("rational_resampler_ccf: ntaps must be in [1, 1024]");
+    if (interp < 1 || interp > 64) throw std::invalid_argument("rational_resampler_ccf: interpolation must be in [1, 64]");
+    if (decim < 1 || decim > 64) throw std::invalid_argument("rational_resampler_ccf: decimation must be in [1, 64]");
+}
+
+bool rational_resampler_ccf::start()
+{
+    _ext.assign((_taps.size() + (size_t)_interp - 1) / (size_t)_interp - 1, gr_complex(0, 0)); // zero history
+    return block::start();
+}
+
+work_return_code_t rational_resampler_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int I = _interp, D = _decim, L = (int)_taps.size();
+    const int n_units = out[0].n_items / I; // resamp_block::do_work: n D inputs, n I outputs
+    const size_t H = (size_t)((L + I - 1) / I - 1), n_in = (size_t)n_units * D;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    _ext.resize(H + n_in);
+    std::memcpy(_ext.data() + H, x, n_in * sizeof(gr_complex));
+    for (int n = 0; n < n_units * I; ++n) {
+        const int phi = (int)(((int64_t)n * D) % I);
+        const gr_complex* w = _ext.data() + H + (size_t)(((int64_t)n * D) / I); // x[j0]
+        float re = 0.f, im = 0.f;
+        for (int k = phi, q = 0; k < L; k += I, ++q) { // the taps that meet a sample, none beyond L
+            re += _taps[k] * w[-q].real();
+            im += _taps[k] * w[-q].imag();
+        }
+        y[n] = gr_complex(re, im);
+    }
+    std::memmove(_ext.data(), _ext.data() + n_in, H * sizeof(gr_complex)); // the last Q-1 raw inputs
+    _ext.resize(H);
+    out[0].n_produced = n_units * I;
     return work_return_code_t::WORK_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
 #include <gnuradio/blocklib/hip/pfb_channelizer_ccf.hpp>
+#include <gnuradio/blocklib/hip/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/rotator_cc.hpp>
 #include <gnuradio/blocklib/hip/synth_source.hpp>
 #include <gnuradio/hip_context.hpp>
@@ -453,6 +454,49 @@ work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, 
     _state.flip();
     ++_launches;
     out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- rational resampler ----------------------------------------------------------------
+rational_resampler_ccf::rational_resampler_ccf(int interp, int decim, const std::vector<float>& taps)
+    : resamp_block("rational_resampler_ccf (hip)", (unsigned)(interp > 0 ? interp : 1), (unsigned)(decim > 0 ? decim : 1)),
+      _taps(taps),
+      _interp(interp),
+      _decim(decim),
+      _state("hip::rational_resampler_ccf", nsh_resamp_plan_destroy)
+{
+    if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::rational_resampler_ccf: ntaps must be in [1, 1024]");
+    if (interp < 1 || interp > 64) throw std::invalid_argument("hip::rational_resampler_ccf: interpolation must be in [1, 64]");
+    if (decim < 1 || decim > 64) throw std::invalid_argument("hip::rational_resampler_ccf: decimation must be in [1, 64]");
+}
+
+rational_resampler_ccf::~rational_resampler_ccf() = default;
+
+std::string rational_resampler_ccf::kernel() const
+{
+    return _state.plan() ? nsh_resamp_kernel(_state.plan()) : std::string();
+}
+
+bool rational_resampler_ccf::start()
+{
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_resamp_plan_create(d, _taps.data(), (int)_taps.size(), _interp, _decim, plan),
+              "hip::rational_resampler_ccf plan");
+        return (size_t)nsh_resamp_history(*plan);
+    });
+    _state.begin_run(current_stream());
+    return block::start();
+}
+
+work_return_code_t rational_resampler_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_units = out[0].n_items / _interp; // resamp_block::do_work: n D inputs, n I outputs
+    check(nsh_resamp_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                         (float*)out[0].buffer->write_ptr(), n_units, current_stream()),
+          "hip::rational_resampler_ccf");
+    _state.flip();
+    ++_launches;
+    out[0].n_produced = n_units * _interp;
     return work_return_code_t::WORK_OK;
 }
 

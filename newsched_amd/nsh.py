@@ -91,6 +91,12 @@ SIGNATURES = {
     "nsh_pfb_tile": (_i, [_vp]),
     "nsh_pfb_kernel": (C.c_char_p, [_vp]),
     "nsh_pfb_channelizer_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_resamp_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, _i, C.POINTER(_vp)]),
+    "nsh_resamp_plan_destroy": (_i, [_vp]),
+    "nsh_resamp_tile": (_i, [_vp]),
+    "nsh_resamp_kernel": (C.c_char_p, [_vp]),
+    "nsh_resamp_history": (_i, [_vp]),
+    "nsh_resamp_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "nsh_fft1024_c2c": (_i, [_vp, _vp, _i64, _i, _vp]),
     "nsh_channelizer1024": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
@@ -320,6 +326,32 @@ class PfbPlan(_Plan):
         check(lib().nsh_pfb_channelizer_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
                                             ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
                                             stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
+
+
+class ResampPlan(_Plan):
+    """Rational resampler by interp / decim (zero-stuff, FIR, decimate in one kernel); see nsh_resamp_ccf."""
+
+    _destroy = "nsh_resamp_plan_destroy"
+
+    def __init__(self, taps, interp: int, decim: int, device: int = 0):
+        t, arr = self._taps_arg(taps)
+        self.ntaps = int(t.size)
+        self.interp = int(interp)
+        self.decim = int(decim)
+        h = C.c_void_p()
+        check(lib().nsh_resamp_plan_create(device, arr, self.ntaps, self.interp, self.decim, C.byref(h)),
+              "nsh_resamp_plan_create")
+        self._h = h
+        self.tile = lib().nsh_resamp_tile(h)
+        self.history = lib().nsh_resamp_history(h)
+        self.kernel = lib().nsh_resamp_kernel(h).decode()
+
+    def __call__(self, x, hist_in, hist_out, y, n_units: int, stream=None):
+        """n_units * interp outputs from n_units * decim inputs; hist_in (or None = zeros) / hist_out:
+        `history` = ceil(ntaps / interp) - 1 raw samples."""
+        check(lib().nsh_resamp_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
+                                   ptr(hist_out) if hist_out is not None else None, ptr(y), n_units,
+                                   stream_ptr(stream)), "nsh_resamp_ccf")
 
 
 class FirCascadePlan(_Plan):

@@ -23,7 +23,8 @@ public:
     std::vector<buffer_sptr> all_buffers() const;
 
     // Items for the edge buffer: 2 * fixed_buf_size / itemsize, at least 2 * D *
-    // output_multiple when the downstream block decimates by D.
+    // output_multiple when the downstream block decimates by D; around an I:D gr::resamp_block at
+    // least 2 * D on the edge into it and 2 * I on the edge out of it.
     size_t get_buffer_num_items(edge_sptr e, flat_graph_sptr fg) const;
 
 private:

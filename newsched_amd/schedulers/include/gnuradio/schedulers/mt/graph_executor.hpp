@@ -1,7 +1,8 @@
 // Runs one pass over a thread's blocks: gathers buffer state, calls do_work(), advances
 // buffers, notifies neighbours (reference schedulers/mt/lib/graph_executor.cpp:7-221 --
 // THE caller of work()). Differences: per-block completion for drain-based termination;
-// WORK_ERROR / WORK_INSUFFICIENT_OUTPUT_ITEMS throw instead of spinning forever (:102-131).
+// WORK_ERROR / WORK_INSUFFICIENT_OUTPUT_ITEMS throw instead of spinning forever (:102-131),
+// except that a gr::resamp_block short of room for one unit's outputs waits for its reader.
 #pragma once
 #include <gnuradio/block.hpp>
 #include <gnuradio/executor.hpp>

@@ -3,6 +3,7 @@
 #include <gnuradio/block.hpp>
 #include <gnuradio/domain_adapter.hpp>
 #include <gnuradio/domain_adapter_direct.hpp>
+#include <gnuradio/resamp_block.hpp>
 #include <gnuradio/schedulers/mt/buffer_management.hpp>
 
 namespace gr {
@@ -69,6 +70,11 @@ size_t buffer_manager::get_buffer_num_items(edge_sptr e, flat_graph_sptr) const
             nitems = std::max(nitems, need);
         }
     }
+    // An I:D block takes D items per unit and makes I: two units on either side of it.
+    if (auto r = std::dynamic_pointer_cast<resamp_block>(e->dst().node()))
+        nitems = std::max(nitems, 2 * (size_t)r->decimation() * (size_t)r->output_multiple());
+    if (auto r = std::dynamic_pointer_cast<resamp_block>(e->src().node()))
+        nitems = std::max(nitems, 2 * (size_t)r->interpolation() * (size_t)r->output_multiple());
     return nitems;
 }
 

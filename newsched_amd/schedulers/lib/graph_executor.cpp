@@ -1,4 +1,5 @@
 // One scheduling pass over a block group (reference schedulers/mt/lib/graph_executor.cpp).
+#include <gnuradio/resamp_block.hpp>
 #include <gnuradio/schedulers/mt/graph_executor.hpp>
 
 #include <climits>
@@ -149,6 +150,8 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
                                     ? std::max(wout[0].n_produced, 0)
                                     : 0);
             if (ret == work_return_code_t::WORK_OK || ret == work_return_code_t::WORK_DONE) break;
+            // an I:D block with a unit to read and fewer than I items of room (resamp_block.hpp)
+            if (ret == work_return_code_t::WORK_INSUFFICIENT_OUTPUT_ITEMS && std::dynamic_pointer_cast<resamp_block>(b)) break;
             if (ret == work_return_code_t::WORK_INSUFFICIENT_INPUT_ITEMS) {
                 if (wout.empty()) break;
                 wout[0].n_items >>= 1; // ask for less output (reference :125-130)
@@ -159,6 +162,10 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
                                      (ret == work_return_code_t::WORK_ERROR ? "WORK_ERROR" : "WORK_INSUFFICIENT_OUTPUT_ITEMS"));
         }
 
+        if (ret == work_return_code_t::WORK_INSUFFICIENT_OUTPUT_ITEMS) { // the reader's post_read wakes it
+            st[id] = S::BLKD_OUT;
+            continue;
+        }
         if (ret == work_return_code_t::WORK_INSUFFICIENT_INPUT_ITEMS) {
             bool writers_done = !in_ports.empty();
             for (auto& p : in_ports)
