@@ -295,7 +295,7 @@ int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, f
  *   y[n] = sum_{k<L} h[k] * u[n*D - k],   u[j*I] = x[j], u = 0 elsewhere
  *        = sum_{q<Q} h[phi + q*I] * x[j0 - q],   phi = (n*D) mod I, j0 = floor(n*D / I), Q = ceil(L / I)
  * (D = 1 is interp_fir_filter_ccf, I = 1 fir_filter_ccf with decimation D). Larger ratios such as
- * 160/147 belong to a pfb_arb_resampler and are out of scope.
+ * 160/147, and rates that are no ratio at all, are nsh_arb_resamp_ccf's (the next section).
  * Per call (one launch of k_resamp<R,P>): n_units units, each D inputs and I outputs: in = n_units*D
  * samples, out = n_units*I samples, so every call starts at phase 0 and the only state is the history.
  * History as nsh_fir_ccf, but Q-1 samples (nsh_resamp_history): hist_in = the Q-1 raw samples before
@@ -320,7 +320,56 @@ int nsh_resamp_history(void* plan);                   /* Q - 1; 0 for NULL */
 int nsh_resamp_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out,
                    int64_t n_units, void* stream);
 
-/* ---- FFT (fft_vcc, 1024-point, unnormalised both ways) ------------------------------
+/* ---- pfb_arb_resampler_ccf: resample by an arbitrary rate (GNU Radio's pfb_arb_resampler) ----
+ * nfilt = F filters (a power of two in [2, 64]; GNU Radio's default is 32), h = taps_host: the real
+ * fp32 prototype with ntaps = L taps (1 <= L <= 2048; Q = ceil(L / F) taps per filter), rate = r output
+ * samples per input sample, finite, 1/64 <= r <= 64; x the complex fp32 input stream. The plan computes
+ * the derivative taps in fp32 on the host, d[k] = fl32(h[k+1] - h[k]) for k < L-1 and d[L-1] = 0 (GNU
+ * Radio's create_diff_taps).
+ * Phase: exact integer arithmetic in place of GNU Radio's float accumulator, so the output does not
+ * depend on how the stream is cut into calls. step = round(F / r * 2^32) (nsh_arb_step; exact from the
+ * double, ties to even) is a uint64 in Q32.32 counted in filter steps; a phase, in the same format, is
+ * the position of a call's output 0 relative to in[0]. Output n of the call is at
+ *   pos(n) = phase + n*step            (exact, unbounded)
+ *   k(n) = pos(n) >> 32,  i(n) = k(n) div F,  j(n) = k(n) mod F,
+ *   mu(n) = float((pos(n) & 0xffffffff) >> 8) * 2^-24     (24 bits: exactly representable)
+ *   y[n] = sum_{q : j + q*F < L} (h[j + q*F] + mu * d[j + q*F]) * x[i(n) - q]
+ * (filter j plus mu times derivative filter j). Taps at k >= L (the padding up to Q*F) are skipped,
+ * never multiplied: a non-finite sample reaches exactly the outputs whose window holds it.
+ * A call has n_in inputs and makes n_out outputs; it needs i(n_out - 1) <= n_in - 1. nsh_arb_span gives
+ *   *n_out      = min(want_out, ceil((n_in*F*2^32 - phase) / step) when that is positive, else 0),
+ *   *n_consumed = c = min(i(*n_out), n_in),     *phase_next = pos(*n_out) - c*F*2^32,
+ * and the next call starts at in + c with phase_next and the history this call wrote. n_out = 0 with
+ * n_in > 0 is a valid, advancing call: it consumes c inputs and hands the history on (a decimator
+ * whose next output lies beyond the items it was given).
+ * nsh_arb_step and nsh_arb_span are host only and make no HIP call. nsh_arb_span refuses a step that
+ * is not that of a rate in [1/64, 64] for this nfilt and n_in or want_out outside [0, 2^31 - 1].
+ * History as nsh_fir_ccf, but Q-1 samples (nsh_arb_history): hist_in = the Q-1 raw samples before in[0]
+ * (NULL = zeros); hist_out receives the Q-1 raw samples before in[c] bit-exactly, must not alias
+ * hist_in and is required when Q > 1. in, out and the histories need only 8-byte alignment (out is
+ * stored 16 bytes wide when it is 16-byte aligned). One launch of k_arb<R,P> per call (none for an
+ * advancing call with Q = 1).
+ * Accuracy: fp32 throughout, in a fixed order per output: q ascending, w = fmaf(mu, d, h), then one
+ * FMA per component, acc = fmaf(w, x, acc). The results are bit-identical however the stream is cut
+ * into calls (with phase and history chained).
+ * Argument errors (NULL pointers, nfilt not a power of two in [2, 64], ntaps outside [1, 2048], a rate
+ * that is not finite or outside [1/64, 64], aliased history, a missing hist_out, a NULL plan, an n_out
+ * larger than nsh_arb_span allows for (phase, n_in), n_in or n_out above 2^31 - 1) are refused before
+ * any HIP call; n_in <= 0 returns 0 and launches nothing.
+ * Measured: DESIGN.md section 4.6. */
+int nsh_arb_step(double rate, int nfilt, uint64_t* step);
+int nsh_arb_span(uint64_t step, int nfilt, uint64_t phase, int64_t n_in, int64_t want_out, int64_t* n_out,
+                 int64_t* n_consumed, uint64_t* phase_next);
+int nsh_arb_plan_create(int dev, const float* taps_host, int ntaps, int nfilt, double rate, void** plan);
+int nsh_arb_plan_destroy(void* plan);                 /* NULL: 0 */
+int nsh_arb_tile(void* plan);                         /* outputs per workgroup; 0 for NULL */
+const char* nsh_arb_kernel(void* plan);               /* e.g. "k_arb<4,1>"; "" for NULL */
+int nsh_arb_history(void* plan);                      /* Q - 1; 0 for NULL */
+int nsh_arb_plan_step(void* plan, uint64_t* step);    /* = nsh_arb_step(rate, nfilt) */
+int nsh_arb_resamp_ccf(void* plan, const float* in, int64_t n_in, const float* hist_in, float* hist_out, float* out,
+                       int64_t n_out, uint64_t phase, void* stream);
+
+/* ---- FFT(fft_vcc, 1024-point, unnormalised both ways) ------------------------------
  * frames of 1024 complex samples; inverse=1 computes sum_k X[k] e^{+2 pi i kn/1024}
  * (= 1024 * numpy.fft.ifft). nsh_channelizer1024 fuses fft -> multiply by w[1024]
  * (complex, device) -> ifft in one pass over HBM, bit-identical to nsh_fft1024_c2c ->

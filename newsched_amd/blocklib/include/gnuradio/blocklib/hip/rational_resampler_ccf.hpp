@@ -2,7 +2,7 @@
 // taps, keep every D-th sample, in one kernel launch per work() (nsh_resamp_ccf, k_resamp<R,P>: every
 // input is read from HBM once and every output written once, 8 B each). Semantics of
 // blocks::rational_resampler_ccf; 1 <= I, D <= 64, at most 1024 taps; larger ratios (160/147) are
-// pfb_arb_resampler territory. D = 1 is interp_fir_filter_ccf.
+// hip::pfb_arb_resampler_ccf's. D = 1 is interp_fir_filter_ccf.
 // A gr::resamp_block: the plan and two (ceil(L / I) - 1)-sample raw-history buffers are created on
 // the first start() on the partition thread, the history is zeroed (or loaded from
 // set_initial_history) on every start().

@@ -2,12 +2,16 @@
 #include <gnuradio/blocklib/blocks/arith.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/blocks/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
 #include <gnuradio/blocklib/blocks/rotator_cc.hpp>
 
+#include "../../csrc/nsh_arb_span.hpp"
+
 #include <algorithm>
+#include <cmath>
 #include <complex>
 #include <cstring>
 #include <stdexcept>
@@ -395,6 +399,61 @@ work_return_code_t rational_resampler_ccf::work(std::vector<block_work_input>& i
     std::memmove(_ext.data(), _ext.data() + n_in, H * sizeof(gr_complex)); // the last Q-1 raw inputs
     _ext.resize(H);
     out[0].n_produced = n_units * I;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- pfb_arb_resampler_ccf: straight from the definition, fp32, exact integer phase ----------------
+pfb_arb_resampler_ccf::pfb_arb_resampler_ccf(double rate, const std::vector<float>& taps, unsigned filter_size)
+    : block("pfb_arb_resampler_ccf"), _rate(rate), _taps(taps), _nfilt(filter_size)
+{
+    _fshift = filter_size <= 64 ? nsh_arb::filt_shift((int)filter_size) : -1;
+    if (_fshift < 0) throw std::invalid_argument("pfb_arb_resampler_ccf: nfilt must be a power of two in [2, 64]");
+    if (taps.empty() || taps.size() > 2048) throw std::invalid_argument("pfb_arb_resampler_ccf: ntaps must be in [1, 2048]");
+    if (!nsh_arb::rate_ok(rate)) throw std::invalid_argument("pfb_arb_resampler_ccf: rate must be finite and in [1/64, 64]");
+    _step = nsh_arb::step_of(rate, (int)filter_size);
+    _diff.resize(taps.size());
+    nsh_arb::diff_taps(_taps.data(), (int)_taps.size(), _diff.data());
+}
+
+bool pfb_arb_resampler_ccf::start()
+{
+    const size_t H = (_taps.size() + _nfilt - 1) / _nfilt - 1;
+    if (!_hist0.empty() && _hist0.size() != H)
+        throw std::runtime_error("pfb_arb_resampler_ccf: the initial history must hold ceil(ntaps / nfilt) - 1 samples");
+    _ext.assign(H, gr_complex(0, 0)); // zero history unless a shard's halo was given
+    if (!_hist0.empty()) _ext = _hist0;
+    _phase = _phase0;
+    return block::start();
+}
+
+work_return_code_t pfb_arb_resampler_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int L = (int)_taps.size(), F = (int)_nfilt;
+    const size_t H = (size_t)((L + F - 1) / F - 1), n_in = (size_t)std::max(in[0].n_items, 0);
+    const nsh_arb::span s = nsh_arb::span_of(_step, _fshift, _phase, (int64_t)n_in, std::max(out[0].n_items, 0));
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    _ext.resize(H + n_in);
+    std::memcpy(_ext.data() + H, x, n_in * sizeof(gr_complex));
+    for (int64_t n = 0; n < s.n_out; ++n) {
+        const unsigned __int128 pos = (unsigned __int128)_phase + (unsigned __int128)(uint64_t)n * _step;
+        const uint64_t k = (uint64_t)(pos >> 32);
+        const float mu = (float)((uint32_t)pos >> 8) * 0x1p-24f;
+        const gr_complex* w = _ext.data() + H + (size_t)(k >> _fshift); // x[i(n)]
+        float re = 0.f, im = 0.f;
+        for (int t = (int)(k & (uint64_t)(F - 1)), q = 0; t < L; t += F, ++q) { // none beyond L
+            const float c = std::fmaf(mu, _diff[t], _taps[t]);
+            re = std::fmaf(c, w[-q].real(), re);
+            im = std::fmaf(c, w[-q].imag(), im);
+        }
+        y[n] = gr_complex(re, im);
+    }
+    std::memmove(_ext.data(), _ext.data() + s.n_consumed, H * sizeof(gr_complex)); // the Q-1 raw inputs before in[c]
+    _ext.resize(H);
+    _phase = s.phase_next;
+    if (s.n_out == 0 && s.n_consumed > 0) ++_advances;
+    out[0].n_produced = (int)s.n_out;
+    in[0].n_consumed = (int)s.n_consumed;
     return work_return_code_t::WORK_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <gnuradio/blocklib/hip/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
+#include <gnuradio/blocklib/hip/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/hip/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/rotator_cc.hpp>
@@ -18,6 +19,7 @@
 #include <cmath>
 #include <stdexcept>
 
+#include "../../csrc/nsh_arb_span.hpp"
 #include "nsh_hip.h"
 
 namespace gr {
@@ -497,6 +499,55 @@ work_return_code_t rational_resampler_ccf::work(std::vector<block_work_input>& i
     _state.flip();
     ++_launches;
     out[0].n_produced = n_units * _interp;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- arbitrary-rate polyphase resampler ------------------------------------------------
+pfb_arb_resampler_ccf::pfb_arb_resampler_ccf(double rate, const std::vector<float>& taps, unsigned filter_size)
+    : block("pfb_arb_resampler_ccf (hip)"),
+      _rate(rate),
+      _taps(taps),
+      _nfilt(filter_size),
+      _state("hip::pfb_arb_resampler_ccf", nsh_arb_plan_destroy)
+{
+    _fshift = filter_size <= 64 ? nsh_arb::filt_shift((int)filter_size) : -1;
+    if (_fshift < 0) throw std::invalid_argument("hip::pfb_arb_resampler_ccf: nfilt must be a power of two in [2, 64]");
+    if (taps.empty() || taps.size() > 2048) throw std::invalid_argument("hip::pfb_arb_resampler_ccf: ntaps must be in [1, 2048]");
+    if (!nsh_arb::rate_ok(rate)) throw std::invalid_argument("hip::pfb_arb_resampler_ccf: rate must be finite and in [1/64, 64]");
+    _step = nsh_arb::step_of(rate, (int)filter_size);
+}
+
+pfb_arb_resampler_ccf::~pfb_arb_resampler_ccf() = default;
+
+std::string pfb_arb_resampler_ccf::kernel() const { return _state.plan() ? nsh_arb_kernel(_state.plan()) : std::string(); }
+
+bool pfb_arb_resampler_ccf::start()
+{
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_arb_plan_create(d, _taps.data(), (int)_taps.size(), (int)_nfilt, _rate, plan), "hip::pfb_arb_resampler_ccf plan");
+        return (size_t)nsh_arb_history(*plan);
+    });
+    _state.begin_run(current_stream());
+    _phase = _phase0;
+    return block::start();
+}
+
+work_return_code_t pfb_arb_resampler_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int64_t n_in = std::max(in[0].n_items, 0);
+    const nsh_arb::span s = nsh_arb::span_of(_step, _fshift, _phase, n_in, std::max(out[0].n_items, 0));
+    // n_out = 0 advances: the kernel only hands the history on
+    check(nsh_arb_resamp_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), n_in, _state.hist_in(), _state.hist_out(),
+                             (float*)out[0].buffer->write_ptr(), s.n_out, _phase, current_stream()),
+          "hip::pfb_arb_resampler_ccf");
+    if (n_in > 0 && (s.n_out > 0 || nsh_arb_history(_state.plan()) > 0)) { // a launch: it wrote hist_out
+        _state.flip();
+        ++_launches;
+    }
+    _phase = s.phase_next;
+    if (s.n_out == 0 && s.n_consumed > 0) ++_advances;
+    out[0].n_produced = (int)s.n_out;
+    in[0].n_consumed = (int)s.n_consumed;
     return work_return_code_t::WORK_OK;
 }
 

@@ -5,7 +5,7 @@
 //        = sum_{q<Q} h[phi + qI] x[j0 - q],   phi = (nD) mod I,  j0 = floor(nD / I),  Q = ceil(L / I)
 //
 // 1 <= I <= 64, 1 <= D <= 64, 1 <= L <= 1024, I and D used as given (not reduced by their gcd).
-// Larger ratios (160/147 and the like) are pfb_arb_resampler territory and out of scope here.
+// Larger ratios (160/147 and the like) and rates that are no ratio are k_arb's (nsh_arb.hip).
 // A call processes n_units units of D inputs and I outputs each, so every call starts at phase 0
 // and the only state is the history: the Q-1 raw samples before in[0].
 //

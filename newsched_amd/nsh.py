@@ -97,6 +97,15 @@ SIGNATURES = {
     "nsh_resamp_kernel": (C.c_char_p, [_vp]),
     "nsh_resamp_history": (_i, [_vp]),
     "nsh_resamp_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_arb_step": (_i, [C.c_double, _i, C.POINTER(_u64)]),
+    "nsh_arb_span": (_i, [_u64, _i, _u64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64)]),
+    "nsh_arb_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.c_double, C.POINTER(_vp)]),
+    "nsh_arb_plan_destroy": (_i, [_vp]),
+    "nsh_arb_tile": (_i, [_vp]),
+    "nsh_arb_kernel": (C.c_char_p, [_vp]),
+    "nsh_arb_history": (_i, [_vp]),
+    "nsh_arb_plan_step": (_i, [_vp, C.POINTER(_u64)]),
+    "nsh_arb_resamp_ccf": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _u64, _vp]),
     "nsh_fft1024_c2c": (_i, [_vp, _vp, _i64, _i, _vp]),
     "nsh_channelizer1024": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
@@ -352,6 +361,57 @@ class ResampPlan(_Plan):
         check(lib().nsh_resamp_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
                                    ptr(hist_out) if hist_out is not None else None, ptr(y), n_units,
                                    stream_ptr(stream)), "nsh_resamp_ccf")
+
+
+def arb_step(rate: float, nfilt: int = 32) -> int:
+    """round(nfilt / rate * 2^32): the Q32.32 step, in filter steps per output, of a rate (nsh_arb_step)."""
+    step = C.c_uint64(0)
+    check(lib().nsh_arb_step(float(rate), int(nfilt), C.byref(step)), "nsh_arb_step")
+    return step.value
+
+
+def arb_span(step: int, nfilt: int, phase: int, n_in: int, want: int):
+    """(n_out, n_consumed, phase_next) of a call with n_in inputs from phase that wants `want` outputs
+    (nsh_arb_span; host only)."""
+    n_out, c, nxt = C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+    check(lib().nsh_arb_span(step, int(nfilt), phase, n_in, want, C.byref(n_out), C.byref(c), C.byref(nxt)),
+          "nsh_arb_span")
+    return n_out.value, c.value, nxt.value
+
+
+class ArbPlan(_Plan):
+    """Arbitrary-rate polyphase resampler (nfilt filters and their derivative filters, exact integer
+    phase, one kernel); see nsh_arb_resamp_ccf."""
+
+    _destroy = "nsh_arb_plan_destroy"
+
+    def __init__(self, taps, rate: float, nfilt: int = 32, device: int = 0):
+        t, arr = self._taps_arg(taps)
+        self.ntaps = int(t.size)
+        self.nfilt = int(nfilt)
+        h = C.c_void_p()
+        check(lib().nsh_arb_plan_create(device, arr, self.ntaps, self.nfilt, float(rate), C.byref(h)),
+              "nsh_arb_plan_create")
+        self._h = h
+        step = C.c_uint64(0)
+        check(lib().nsh_arb_plan_step(h, C.byref(step)), "nsh_arb_plan_step")
+        self.step = step.value
+        self.rate_effective = self.nfilt * 2.0**32 / self.step
+        self.tile = lib().nsh_arb_tile(h)
+        self.history = lib().nsh_arb_history(h)
+        self.kernel = lib().nsh_arb_kernel(h).decode()
+
+    def span(self, phase: int, n_in: int, want: int):
+        """(n_out, n_consumed, phase_next): what a call with n_in inputs from phase can make of `want`."""
+        return arb_span(self.step, self.nfilt, phase, n_in, want)
+
+    def __call__(self, x, n_in: int, hist_in, hist_out, y, n_out: int, phase: int = 0, stream=None):
+        """n_out outputs (at most span(phase, n_in, ...)) from n_in inputs; hist_in (or None = zeros) /
+        hist_out: `history` = ceil(ntaps / nfilt) - 1 raw samples. n_out = 0 only advances."""
+        check(lib().nsh_arb_resamp_ccf(self._h, ptr(x), n_in, ptr(hist_in) if hist_in is not None else None,
+                                       ptr(hist_out) if hist_out is not None else None,
+                                       ptr(y) if y is not None else None, n_out, phase,
+                                       stream_ptr(stream)), "nsh_arb_resamp_ccf")
 
 
 class FirCascadePlan(_Plan):
