@@ -4,7 +4,10 @@
 #include <hip/hip_ext.h>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
+#include <set>
 #include <string>
+#include <utility>
 
 #include "nsh_hip.h"
 
@@ -94,6 +97,20 @@ inline void launch_timed(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStrea
 struct launch_events_guard {
     ~launch_events_guard() { next_launch_events() = launch_events(); }
 };
+
+// The dynamic-LDS limit of a kernel, set once per (kernel, device): hipFuncSetAttribute acts on
+// the current device, so a process-wide flag would leave a second device's launches unset. bytes
+// is the most any launch of fn asks for (a later call with another value would be skipped).
+inline hipError_t set_lds_attr(const void* fn, int bytes, int dev)
+{
+    static std::mutex m;
+    static std::set<std::pair<const void*, int>> done;
+    std::lock_guard<std::mutex> g(m);
+    if (done.count({ fn, dev })) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.insert({ fn, dev });
+    return e;
+}
 
 // Grid for a grid-stride streaming kernel: enough workgroups to fill 256 CUs several
 // times over, capped so each thread still walks several 16-byte vectors.

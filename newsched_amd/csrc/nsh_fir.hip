@@ -111,12 +111,41 @@ __global__ __launch_bounds__(kThreads) void k_fir_direct(const float2* __restric
     }
 }
 
+// Dynamic LDS of k_fir_direct<D, R> at Lp padded taps: the staged window and its pad samples.
+template <int D, int R>
+constexpr size_t direct_lds(int Lp)
+{
+    const int count = (kThreads * R - 1) * D + Lp;
+    return (size_t)(count + count / (R * D) + 1) * sizeof(float2);
+}
+
+// The kernel's dynamic-LDS limit, raised to what its longest filter asks for (4096 taps: 55288
+// bytes at decim 1, 69616 / 69616 / 69568 at decim 2 / 4 / 8 -- past 64 KiB from 3617 taps), as
+// for every other kernel of the library with dynamic LDS. Plan creation calls it too, so a shape
+// whose launch the runtime would refuse never gets a plan.
+template <int D, int R>
+hipError_t direct_lds_attr(int dev)
+{
+    return nsh::set_lds_attr((const void*)k_fir_direct<D, R>, (int)direct_lds<D, R>(4096), dev);
+}
+
+hipError_t prepare_direct(const nsh_fir_plan* p)
+{
+    switch (p->D) {
+    case 1: return direct_lds_attr<1, 8>(p->dev);
+    case 2: return direct_lds_attr<2, 8>(p->dev);
+    case 4: return direct_lds_attr<4, 4>(p->dev);
+    case 8: return direct_lds_attr<8, 2>(p->dev);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 template <int D, int R>
 int launch_direct(const nsh_fir_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out, hipStream_t s)
 {
     constexpr int T = kThreads * R;
-    const int count = (T - 1) * D + p->Lp;
-    const size_t lds = (size_t)(count + count / (R * D) + 1) * sizeof(float2);
+    const size_t lds = direct_lds<D, R>(p->Lp);
+    NSH_CK((direct_lds_attr<D, R>(p->dev)));
     const int64_t grid = (n_out + T - 1) / T;
     if (grid > 0x7fffffff) return nsh::fail_msg("nsh_fir_ccf: too many outputs for one call");
     nsh::launch((k_fir_direct<D, R>), dim3((unsigned)grid), dim3(kThreads), lds, s,
@@ -209,6 +238,7 @@ int nsh_fir_plan_create(int dev, const float* taps_host, int ntaps, int decim, i
     }
     p->algo = resolved;
     if (resolved == NSH_FIR_DIRECT) {
+        if ((e = prepare_direct(p.get())) != hipSuccess) return nsh::fail(e, "nsh_fir_plan_create: direct form's LDS limit");
         static const int R[9] = { 0, 8, 8, 0, 4, 0, 0, 0, 2 };
         p->kernel = "k_fir_direct<" + std::to_string(p->D) + "," + std::to_string(R[p->D]) + ">";
     } else if (resolved == NSH_FIR_MFMA_F32) {

@@ -169,23 +169,12 @@ __global__ __launch_bounds__(256) void k_fir_f32mfma(const float2* __restrict__ 
         }
 }
 
-hipError_t set_lds_attr_f32(const void* fn, int bytes, int dev)
-{
-    static std::mutex m;
-    static std::set<std::pair<const void*, int>> done;
-    std::lock_guard<std::mutex> g(m);
-    if (done.count({ fn, dev })) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done.insert({ fn, dev });
-    return e;
-}
-
 template <int QF>
 int launch_f32(const nsh_fir_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out,
                hipStream_t s)
 {
     using G = geomf32<QF>;
-    NSH_CK(set_lds_attr_f32((const void*)k_fir_f32mfma<QF>, G::LDS, p->dev));
+    NSH_CK(nsh::set_lds_attr((const void*)k_fir_f32mfma<QF>, G::LDS, p->dev));
     const int64_t nchunks = (n_out + G::CHUNK - 1) / G::CHUNK;
     const int64_t per_x = (nchunks + 7) / 8;
     const int64_t grid = per_x * 8;

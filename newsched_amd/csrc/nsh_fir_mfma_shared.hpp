@@ -15,25 +15,13 @@ namespace {
 // may be shared by concurrent launches)
 int plan_cus(const nsh_fir_plan* p) { return p->n_cu > 0 ? p->n_cu : 256; }
 
-// The dynamic-LDS limit of a kernel, set once per (kernel, device): hipFuncSetAttribute acts on
-// the current device, so a process-wide flag would leave a second device's launches unset.
-hipError_t set_lds_attr(const void* fn, int bytes, int dev)
-{
-    static std::mutex m;
-    static std::set<std::pair<const void*, int>> done;
-    std::lock_guard<std::mutex> g(m);
-    if (done.count({ fn, dev })) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done.insert({ fn, dev });
-    return e;
-}
-
 using nsh::AUX_NT;
 using nsh::buf_load_f4;
 using nsh::buf_store_f2;
 using nsh::chunk_rsrc;
 using nsh::nf2;
 using nsh::nf4;
+using nsh::set_lds_attr;
 using nsh::u32x2;
 using nsh::virt;
 

@@ -1024,16 +1024,7 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
     }
 }
 
-hipError_t set_lds_attr(const void* fn, int bytes, int dev)
-{
-    static std::mutex mtx;
-    static std::set<std::pair<const void*, int>> done;
-    std::lock_guard<std::mutex> g(mtx);
-    if (done.count({ fn, dev })) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done.insert({ fn, dev });
-    return e;
-}
+using nsh::set_lds_attr;
 
 // Phases per wave. Two per wave (8 waves at P = 16, half the product and reduction LDS traffic,
 // two independent transforms per wave) measured 650 vs 600 us per 2^28 inputs against one per

@@ -159,6 +159,8 @@ def test_mul_const_vcc_bitexact(torch_cuda, vlen, nitems):
 # "mfma" is the default matrix-core kernel (decim 1: per-chunk scaled fp16x2, k_fir_mfma12),
 # "mfma_f32" the exact-fp32 matrix form (k_fir_f32mfma)
 ALGOS = [("direct", nsh.FIR_DIRECT), ("mfma", nsh.FIR_MFMA), ("mfma_f32", nsh.FIR_MFMA_F32)]
+# The limit of each form. The sweeps below stop at 161 taps: the direct form from 162 to its 4096
+# and every tap-count bucket of the matrix forms are run by tests/test_gpu_fir_forms.py.
 MAX_TAPS = {"direct": 4096, "mfma": 161, "mfma_f32": 257}
 
 

@@ -190,3 +190,26 @@ def test_synth_oracle_wraps_at_2_64():
     np.testing.assert_array_equal(orc.synth(8), gg.synth(8))
     assert orc.synth(2, 2 ** 63 - 1)[1] == orc.synth(1, 0)[0]  # 2 * 2^63 wraps to 0
     np.testing.assert_array_equal(orc.synth(100, 2 ** 63 + 5), orc.synth(100, 5))
+
+
+# ---- what tests/test_gpu_fir_forms.py leans on ----------------------------------------------------
+def test_fir_oracle_integer_class_is_exact():
+    """Integer taps, samples and history in [-8, 8] at 4096 taps: every sum is an integer far below
+    2^24, so the oracle (double accumulation, one rounding to fp32) equals an int64 convolution
+    exactly -- outputs and hist_out, at decim 1 and 8. The bit-equality the GPU tests demand of the
+    kernels on this data class rests on this."""
+    L = 4096
+    rng = np.random.default_rng(4096)
+    h = rng.integers(-8, 9, L)
+    h[0], h[-1] = 3, -5
+    for D in (1, 8):
+        n_out = 1027
+        s = rng.integers(-8, 9, (2, L - 1 + n_out * D))  # history, then the input; real and imaginary rows
+        z = (s[0] + 1j * s[1]).astype(np.complex64)
+        y, hout = orc.fir_ccf(z[L - 1:], h.astype(np.float32), D, hist=z[: L - 1], return_hist=True)
+        full = [np.convolve(part.astype(np.int64), h.astype(np.int64))[L - 1: L - 1 + n_out * D: D] for part in s]
+        assert max(int(np.abs(f).max()) for f in full) < 2 ** 24
+        np.testing.assert_array_equal(y.real.astype(np.int64), full[0])
+        np.testing.assert_array_equal(y.imag.astype(np.int64), full[1])
+        assert np.all(y.real == np.round(y.real)) and np.all(y.imag == np.round(y.imag))
+        np.testing.assert_array_equal(hout, z[-(L - 1):])
