@@ -15,7 +15,8 @@
 //    are padded by one sample every R*D samples so the per-lane ds_read_b64 of the window
 //    is bank-conflict-free. Exact fp32 products, fp32 accumulation in tap order.
 //  * MFMA -- split-precision Toeplitz MFMA (nsh_fir_mfma.hip): decim 1 on 32-sample blocks as
-//    scaled fp16x2 (k_fir_mfma12), decim 2 and 4 as the polyphase fp16x2 form (k_fir_mfma11).
+//    scaled fp16x2 (k_fir_mfma12), decim 2 and 4 as the polyphase fp16x2 form (k_fir_mfma13, or
+//    k_fir_mfma11 on the contiguous walk).
 //  * MFMA_F32 -- exact fp32 Toeplitz MFMA (nsh_fir_f32.hip); PFFT -- decim 8 / 16 by
 //    polyphase-FFT overlap-save (nsh_fir_pfft.hip). Decim 8 otherwise: DIRECT.
 //  NSH_FIR_MFMA16 / NSH_FIR_MFMA_BF16X3 name kernels retired in round 4 (DESIGN.md section 4

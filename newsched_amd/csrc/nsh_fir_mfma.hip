@@ -2,7 +2,11 @@
 //
 //   k_fir_mfma12<Q>      decim 1 (the C3 bench kernel)
 //   k_fir_exact12<Q>     decim 1: the chunks k_fir_mfma12 queued for an exact form (same call, same stream)
-//   k_fir_mfma11<D, QH>  decim 2 and 4 (polyphase; the staged C5 chain's stages)
+//   k_fir_mfma13<D, QH>  decim 2 and 4 (polyphase; the staged C5 chain's stages): the XCD-lockstep walk,
+//                        the default
+//   k_fir_exact13<D, QH> decim 2 and 4: the chunks k_fir_mfma13 queued for an exact form
+//   k_fir_mfma11<D, QH>  decim 2 and 4 on the contiguous walk, exact forms inline (NSH_DEC_WALK_MASK
+//                        selects it; the tests run both walks)
 //
 // Blocked Toeplitz form. Split the output stream into 32-sample blocks; output n = 32*beta + i:
 //     y[32 beta + i] = sum_{q<Q} sum_{r<32} h[i - r + 32 q] * x[32 (beta - q) + r]
@@ -15,8 +19,8 @@
 // scale (taps once on the host, samples per 2048-sample chunk), three products
 // x0h0 + x0h1 + x1h0 accumulated in fp32 (see the fp16x2 notes in nsh_fir_mfma_shared.hpp and
 // below); chunks whose range the split cannot hold take the exact-fp32 matrix tile, chunks holding
-// inf/NaN the fp32 direct form (exact IEEE semantics) -- at decim 1 in k_fir_exact12, at decim 2
-// and 4 inside the same launch.
+// inf/NaN the fp32 direct form (exact IEEE semantics) -- in k_fir_exact12 / k_fir_exact13, launched
+// right after the main kernel on the same stream, or inside k_fir_mfma11 itself.
 //
 // The forms this file superseded -- k_fir_mfma2 (bf16x3, six products), k_fir_mfma5 (16-sample
 // blocks), k_fir_mfma7 (bf16x3 decimator), k_fir_mfma9 (v12's predecessor) and k_fir_casc2 (two
@@ -25,10 +29,7 @@
 #include "nsh_fir_mfma_shared.hpp"
 #include "nsh_fir_f32_tile.hpp"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -181,10 +182,100 @@ __host__ __device__ constexpr int64_t xq_subcap(int64_t grid) { return (grid + X
 #define NSH_X12_PER_CU 5 // k_fir_exact12 workgroups per CU (a persistent walk over the queue) = its waves per SIMD
 #endif
 
-// chunk ch -> registers (nontemporal) and its halo (default policy: the previous chunk's tail was
-// just read by the previous workgroup of this XCD). Branch-free: the halo comes through one buffer
-// resource, over `in` (ch > 0) or over hist_in (ch = 0; out-of-range lanes and a null history
-// read zeros), so no wait sits between the loads.
+// A main kernel's workgroup queues chunk ch (m: its largest magnitude, non-finite -> the direct
+// form) for the launch's exact kernel: a vector atomic and a vector store, from one lane.
+template <class Cap> // subcap(): the sub-queues' capacity, read only after the atomic (k_fir_mfma12 derives it from its grid)
+__device__ __forceinline__ void xq_append(unsigned* xq, Cap subcap, int64_t ch, unsigned m)
+{
+    const unsigned k = blockIdx.x % XQ_N;
+    const unsigned i = __hip_atomic_fetch_add(xq + XQ_LINE * k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // i < subcap always, on a queue whose counters were zeroed (xq_reset after a failed
+    // call): the bound keeps a stale counter from writing into the next sub-queue, and
+    // the exact kernel refilters the whole launch if the count ever exceeds it
+    if (i < (unsigned)subcap())
+        __hip_atomic_store(xq + XQ_E + k * subcap() + i, (unsigned)(ch << 1) | (m >= 0x7f800000u ? 1u : 0u), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// An exact kernel's view of its launch's queue, the same in every wave: cnt entries, entry(i) =
+// (chunk << 1) | direct form. Constructing it also zeroes the next launch's counters.
+struct xq_reader {
+    static_assert(XQ_N == 64, "one sub-queue counter per lane");
+    const unsigned* xq;
+    int64_t subcap;
+    unsigned incl; // lane k: entries in sub-queues 0..k
+    bool over;
+    int64_t nchunks; // of the launch (chunk output samples each)
+    unsigned cnt;
+    __device__ __forceinline__ xq_reader(const unsigned* __restrict__ xq_, unsigned* __restrict__ xq_next, int64_t subcap_,
+                                         int64_t n_out, int chunk, int tid)
+        : xq(xq_), subcap(subcap_)
+    {
+        const int lane = tid & 63;
+        if (blockIdx.x == 0 && tid < 64) // the next launch's counters (vector stores, one lane each)
+            __hip_atomic_store(xq_next + XQ_LINE * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // every wave: the XQ_N counters (one per lane) and their inclusive prefix sum
+        incl = __hip_atomic_load(xq + XQ_LINE * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // a sub-queue that counted more appends than it holds lost entries (never on a queue whose
+        // counters were zeroed: xq_reset after a failed call): then every chunk of the
+        // launch is filtered again here in the fp32 direct form -- slow, but no output is left unwritten
+        over = __ballot(incl > (unsigned)subcap) != 0;
+        incl = min(incl, (unsigned)subcap); // entries past a sub-queue's capacity were never written
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        nchunks = (n_out + chunk - 1) / chunk;
+        cnt = over ? (unsigned)nchunks : __builtin_amdgcn_readlane(incl, 63);
+    }
+    __device__ __forceinline__ unsigned entry(unsigned i) const
+    {
+        if (over) return (i << 1) | 1u; // chunk i, direct form
+        const int k = __popcll(__ballot(incl <= i)); // sub-queue holding queued chunk i (prefix sums ascend)
+        const unsigned start = k ? __shfl(incl, k - 1) : 0u;
+        return __hip_atomic_load(xq + XQ_E + k * subcap + (i - start), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// The HN input samples before chunk ch (of CHUNK samples) -> hv, two per thread tid < HN / 2,
+// default cache policy (the previous chunk's tail was just read by a neighbouring workgroup of this
+// XCD). Branch-free: they come through one buffer resource, over `in` (ch > 0) or over hist_in
+// (ch = 0: element g + L - 1; out-of-range lanes and a null history read zeros), so no wait sits
+// between the loads. PAST: ch may lie past the stream's n_in samples (an empty prefetch): zeros.
+template <int HN, int CHUNK, bool PAST>
+__device__ __forceinline__ void load_halo(const float2* __restrict__ in, const float2* __restrict__ hist_in, int L, int64_t n_in,
+                                          int64_t ch, int tid, float4& hv)
+{
+    __amdgpu_buffer_rsrc_t hr;
+    int off0, off1; // per sample: with an odd history length a pair straddles its start
+    if (ch > 0) {
+        hr = chunk_rsrc<HN>(in + ch * CHUNK - HN, 0, !PAST || ch * CHUNK <= n_in ? HN : 0);
+        off0 = 16 * tid;
+        off1 = off0 + 8;
+    } else {
+        hr = chunk_rsrc<1 << 20>(hist_in, 0, hist_in ? L - 1 : 0);
+        const int e = 2 * tid - HN + (L - 1); // history element of the lane's first sample
+        off0 = e >= 0 ? 8 * e : 1 << 30;      // past num_records -> zeros
+        off1 = e + 1 >= 0 ? 8 * (e + 1) : 1 << 30;
+    }
+    hv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < HN / 2) {
+        const nsh::buf_f2 a = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off0, 0, 0));
+        const nsh::buf_f2 b = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off1, 0, 0));
+        hv = make_float4(a.x, a.y, b.x, b.y);
+    }
+}
+
+// the last L - 1 inputs of the call, for the next one
+template <int NT>
+__device__ __forceinline__ void put_hist_tail(float2* __restrict__ hist_out, const float2* __restrict__ in,
+                                              const float2* __restrict__ hist_in, int64_t n_in, int L)
+{
+    for (int j = threadIdx.x; j < L - 1; j += NT) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
+}
+
+// chunk ch -> registers (nontemporal) and its halo
 template <int Q>
 __device__ __forceinline__ void load12(const float2* __restrict__ in, const float2* __restrict__ hist_in, int L,
                                        int64_t n_in, int64_t ch, float4 (&v)[4], float4& hv)
@@ -192,24 +283,7 @@ __device__ __forceinline__ void load12(const float2* __restrict__ in, const floa
     using G = geom12<Q>;
     const int tid = threadIdx.x;
     load_chunk9(v, in, ch, n_in);
-    __amdgpu_buffer_rsrc_t hr;
-    int off0, off1; // per sample: with an odd history length a pair straddles its start
-    if (ch > 0) {
-        hr = chunk_rsrc<G::H>(in + ch * G::CHUNK - G::H, 0, G::H);
-        off0 = 16 * tid;
-        off1 = off0 + 8;
-    } else {
-        hr = chunk_rsrc<1 << 20>(hist_in, 0, hist_in ? L - 1 : 0);
-        const int e = 2 * tid - G::H + (L - 1); // history element of the lane's first sample
-        off0 = e >= 0 ? 8 * e : 1 << 30;         // past num_records -> zeros
-        off1 = e + 1 >= 0 ? 8 * (e + 1) : 1 << 30;
-    }
-    hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < G::HP) {
-        const nsh::buf_f2 a = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off0, 0, 0));
-        const nsh::buf_f2 b = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off1, 0, 0));
-        hv = make_float4(a.x, a.y, b.x, b.y);
-    }
+    load_halo<G::H, G::CHUNK, false>(in, hist_in, L, n_in, ch, tid, hv);
 }
 
 // One chunk on an exact form, from its samples in registers: finite -> the exact-fp32 tile, else the
@@ -324,6 +398,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     const int h = lane >> 5;
     const int phase = rho;
     {   // chunk + halo range -> workgroup scale and exact-path decision
+        // open-coded wave_range: through the helper one register initialisation moves, and this kernel's
+        // instruction stream is kept as measured
         float mf = max_abs4(hv);
         unsigned z = min_nz1(hv);
 #pragma unroll
@@ -340,21 +416,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     }
     nsh::lds_barrier();
     // workgroup-uniform, and made provably so (SGPRs): the branch on it is a scalar branch
-    const unsigned m = __builtin_amdgcn_readfirstlane(max(max(slot_max[0], slot_max[1]), max(slot_max[2], slot_max[3])));
-    const unsigned z = __builtin_amdgcn_readfirstlane(min(min(slot_mnz[0], slot_mnz[1]), min(slot_mnz[2], slot_mnz[3])));
+    const unsigned m = __builtin_amdgcn_readfirstlane(slots_max(slot_max));
+    const unsigned z = __builtin_amdgcn_readfirstlane(slots_min(slot_mnz));
     const int s = scale_of(m);
     if (__builtin_expect(chunk_needs_exact(m, z, s), 0)) {
-        // k_fir_exact12 filters it (a vector atomic and a vector store from one lane)
-        if (tid == 0) {
-            const unsigned k = blockIdx.x % XQ_N;
-            const unsigned i = __hip_atomic_fetch_add(xq + XQ_LINE * k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // i < subcap always, on a queue whose counters were zeroed (xq_reset after a failed
-            // call): the bound keeps a stale counter from writing into the next sub-queue, and
-            // k_fir_exact12 refilters the whole launch if the count ever exceeds it
-            if (i < (unsigned)xq_subcap(gridDim.x))
-                __hip_atomic_store(xq + XQ_E + k * xq_subcap(gridDim.x) + i, (unsigned)(ch << 1) | (m >= 0x7f800000u ? 1u : 0u),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (tid == 0) xq_append(xq, [] { return xq_subcap(gridDim.x); }, ch, m); // k_fir_exact12 filters it
     } else {
         if (tid < G::HP) store_pair12<Q>(hv, lds, 2 * tid, s);
 #pragma unroll
@@ -419,8 +485,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(nsh::u32x2, o[reg]), r, lb, 256 * ((reg & 3) + 8 * (reg >> 2)),
                                                   nsh::AUX_ST);
     }
-    if (ch == 0) // the last L-1 inputs for the next call (after this workgroup's stores)
-        for (int j = tid; j < L - 1; j += G::NT) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
+    if (ch == 0) put_hist_tail<G::NT>(hist_out, in, hist_in, n_in, L); // after this workgroup's stores
 }
 
 // The chunks k_fir_mfma12 queued: a persistent walk over the queue (NSH_X12_PER_CU workgroups per
@@ -439,35 +504,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSH_X12_PER
                                                     int64_t n_out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    static_assert(XQ_N == 64, "one sub-queue counter per lane");
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    if (blockIdx.x == 0 && tid < 64) // the next launch's counters (vector stores, one lane each)
-        __hip_atomic_store(xq_next + XQ_LINE * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // every wave: the XQ_N counters (one per lane) and their inclusive prefix sum
-    unsigned incl = __hip_atomic_load(xq + XQ_LINE * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // a sub-queue that counted more appends than it holds lost entries (never on a queue whose
-    // counters were zeroed: xq_reset after a failed call): then every chunk of the
-    // launch is filtered again here in the fp32 direct form -- slow, but no output is left unwritten
-    const bool over = __ballot(incl > (unsigned)subcap) != 0;
-    incl = min(incl, (unsigned)subcap); // entries past a sub-queue's capacity were never written
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const int64_t nchunks = (n_out + geom12<Q>::CHUNK - 1) / geom12<Q>::CHUNK;
-    const unsigned cnt = over ? (unsigned)nchunks : __builtin_amdgcn_readlane(incl, 63);
-    if (cnt == 0) return; // nothing queued (the common case)
-    auto entry = [&](unsigned i) {
-        if (over) return (i << 1) | 1u; // chunk i, direct form
-        const int k = __popcll(__ballot(incl <= i)); // sub-queue holding queued chunk i (prefix sums ascend)
-        const unsigned start = k ? __shfl(incl, k - 1) : 0u;
-        return __hip_atomic_load(xq + XQ_E + k * subcap + (i - start), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    for (unsigned i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const unsigned e = entry(i);
-        if ((int64_t)(e >> 1) >= nchunks) continue; // never for a queue this launch filled (defensive)
+    const xq_reader q(xq, xq_next, subcap, n_out, geom12<Q>::CHUNK, tid);
+    if (q.cnt == 0) return; // nothing queued (the common case)
+    for (unsigned i = blockIdx.x; i < q.cnt; i += gridDim.x) {
+        const unsigned e = q.entry(i);
+        if ((int64_t)(e >> 1) >= q.nchunks) continue; // never for a queue this launch filled (defensive)
         float4 v[4], hv;
         load12<Q>(in, hist_in, L, n_out, e >> 1, v, hv);
         exact_chunk12<Q>(lds, out, timg32, taps, L, n_out, e >> 1, v, hv, NSH_V12_F32T && !(e & 1u));
@@ -498,6 +540,98 @@ struct geom11x : geom11<D, QH> {
     static_assert(2 * LDS <= 160 * 1024, "2 workgroups per CU");
 };
 
+// chunk (registers; v[u D + f] is its float4 q_of(u, f)) and the thread's halo float4 *h (tid < HP)
+// -> buf for an exact form: the tile's fp32 planes (16-sample rows), or raw fp32 (halo float4
+// [0, HP), chunk float4 HP + j), halo first
+template <int D, int QH, class QOf>
+__device__ __forceinline__ void stage_exact11(int tid, unsigned char* buf, const float4* h, const float4 (&v)[4], bool f32t, QOf q_of)
+{
+    using G = geom11x<D, QH>;
+    using GF = typename G::GF;
+    if (f32t) {
+        if (tid < G::HP) nsh_f32t::put<GF>(buf, *h, 2 * tid);
+#pragma unroll
+        for (int u = 0; u < G::UNITS; ++u)
+#pragma unroll
+            for (int f = 0; f < D; ++f) nsh_f32t::put<GF>(buf, v[u * D + f], GF::H + 2 * q_of(u, f));
+    } else {
+        float4* rb = reinterpret_cast<float4*>(buf);
+        if (tid < G::HP) rb[tid] = *h;
+#pragma unroll
+        for (int u = 0; u < G::UNITS; ++u)
+#pragma unroll
+            for (int f = 0; f < D; ++f) rb[G::HP + q_of(u, f)] = v[u * D + f];
+    }
+}
+
+// The exact-fp32 tile on a chunk staged at cur: the tile's outputs n = 16 (32 wave + 8 t + 2 g + u) + i
+// (undecimated), the lanes with i mod D = 0 keeping theirs (m = n / D), through the wave's LDS
+// scratch into the split path's lane map (the wave's own outputs: a wave barrier, no workgroup
+// barrier)
+template <int D, int QH>
+__device__ __forceinline__ void f32_tile11(const unsigned char* cur, unsigned char* lds, const lane11<D, QH>& ln,
+                                           nf2 (&o)[2 * geom11<D, QH>::TILES])
+{
+    using G = geom11x<D, QH>;
+    const int g = ln.g;
+    f32x4 acc[4];
+    nsh_f32t::tile_at<typename G::GF, G::QF>(cur, lds + G::TAPF, ln.wave, ln.lane, acc);
+    nf2* scr = reinterpret_cast<nf2*>(lds + G::SCR) + ln.wave * G::WAVE_OUT;
+    const int i = ln.lane & 15;
+    if (i % D == 0) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) scr[(16 * (8 * t + 2 * g + u) + i) / D] = nf2{ acc[t][2 * u], acc[t][2 * u + 1] };
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int oi = 0; oi < 2 * G::TILES; ++oi) o[oi] = scr[((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + ln.phase];
+}
+
+// The fp32 direct form on a raw chunk staged at cur: y[m] = sum_k h[k] x[D m - k] (float2 index
+// D H + D m - k). D = 4: outputs 0 and 1 are 64 input samples apart and share their inputs
+// (direct_group; decim_qh gives L - 1 <= D H and every k <= D (H - 16) below L): dense-exact
+// floor 74.7 -> 97.6 GS/s input. D = 2 keeps one output at a time: its two unrolled groups
+// cost k_fir_mfma11's main path a third of its speed (594 -> 890 us per 2^28, profiles/r02o_*).
+template <int D, int QH>
+__device__ __forceinline__ void direct_tile11(const unsigned char* cur, const float* __restrict__ taps, int L,
+                                              const lane11<D, QH>& ln, nf2 (&o)[2 * geom11<D, QH>::TILES])
+{
+    using G = geom11<D, QH>;
+    const int wave = ln.wave, g = ln.g, phase = ln.phase;
+    if constexpr (D == 4 || NSH_DECIM2_SHARED) {
+#pragma unroll 1
+        for (int t = 0; t < G::TILES; ++t) {
+            nf2 acc[2];
+            direct_group<2, 16 * D, D * G::H, D * (G::H - 16)>(
+                reinterpret_cast<const nf2*>(cur), D * G::H + D * (wave * G::WAVE_OUT + (8 * t + 2 * g) * 16 + phase), taps, L, acc);
+            if (t == 0) {
+                o[0] = acc[0];
+                o[1] = acc[1];
+            } else {
+                o[2 * G::TILES - 2] = acc[0];
+                o[2 * G::TILES - 1] = acc[1];
+            }
+        }
+    } else {
+        const float2* raw = reinterpret_cast<const float2*>(cur);
+        for (int oi = 0; oi < 2 * G::TILES; ++oi) {
+            const int blk = (oi >> 1) * 8 + 2 * g + (oi & 1);
+            const int j = D * G::H + D * (wave * G::WAVE_OUT + blk * 16 + phase);
+            float re = 0.f, im = 0.f;
+            for (int k = 0; k < L; ++k) {
+                const float2 x = raw[j - k];
+                re = fmaf(taps[k], x.x, re);
+                im = fmaf(taps[k], x.y, im);
+            }
+            o[oi] = nf2{ re, im };
+        }
+    }
+}
+
 template <int D, int QH>
 __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict__ in,
                                                       const float2* __restrict__ hist_in,
@@ -513,15 +647,14 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
     using G = geom11x<D, QH>;
     using GF = typename G::GF;
     constexpr int KS = G::KS;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     float4* stash = reinterpret_cast<float4*>(lds + G::STASH_AT); // [2][HP] raw halo sources
     unsigned* slot_max = reinterpret_cast<unsigned*>(lds + G::SLOTS);
     unsigned* slot_mnz = slot_max + 8;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const lane11<D, QH> ln(tid);
+    const int lane = ln.lane, wave = ln.wave;
     const int64_t n_in = n_out * D;
     {   // the tile's taps, once per workgroup (read after the prologue's barriers)
         float4 t32[2];
@@ -529,9 +662,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
         nsh_f32t::put_taps_at<GF>(lds + G::TAPF, t32, tid, G::NT);
     }
 
-    if (blockIdx.x == 0) {
-        for (int j = tid; j < L - 1; j += G::NT) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
-    }
+    if (blockIdx.x == 0) put_hist_tail<G::NT>(hist_out, in, hist_in, n_in, L);
 
     f16x8 B0[D][KS + 1], B1[D][KS + 1];
     f16x4 T0[D], T1[D];
@@ -555,11 +686,6 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
     if (c_begin >= c_end) return;
     const int64_t c_last = c_end - 1;
 
-    const int rho = lane & 15;
-    const int c = rho & 1, b = rho >> 1;
-    const int g = lane >> 4;
-    const int phase = lane & 15;
-    const int row_base = c * G::IM_OFF + (G::HR + wave * (G::WAVE_OUT / 16) + b) * 32;
     const bool tail_owner = tid >= G::NT - G::H / 2; // holds the chunk's last D*H samples (last unit)
     // prefetch index: past the workgroup's range, an empty buffer range (loads return 0 and move
     // no bytes; a re-load of the last chunk would go to HBM again, the loads are nontemporal)
@@ -581,169 +707,15 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
             for (int f = 0; f < D; ++f) st[(tid - (G::NT - G::H / 2)) * D + f] = v[(G::UNITS - 1) * D + f];
         }
     };
-    // chunk -> buffer: raw fp32 (halo float4 [0, HP), chunk float4 HP + j) or split phase planes
+    // chunk -> buffer: staged for an exact form (raw; f32t: the tile's planes) or split phase planes
     auto put_chunk = [&](unsigned char* buf, const float4* hsrc, const float4 (&v)[4], bool raw, bool f32t, int sc) {
-        if (__builtin_expect(f32t, 0)) { // the tile's fp32 planes (16-sample rows), halo first
-            if (tid < G::HP) nsh_f32t::put<GF>(buf, hsrc[tid], 2 * tid);
-#pragma unroll
-            for (int u = 0; u < G::UNITS; ++u)
-#pragma unroll
-                for (int f = 0; f < D; ++f) nsh_f32t::put<GF>(buf, v[u * D + f], GF::H + 2 * ((tid + G::NT * u) * D + f));
-            return;
-        }
-        if (raw) {
-            float4* rb = reinterpret_cast<float4*>(buf);
-            if (tid < G::HP) rb[tid] = hsrc[tid];
-#pragma unroll
-            for (int u = 0; u < G::UNITS; ++u)
-#pragma unroll
-                for (int f = 0; f < D; ++f) rb[G::HP + (tid + G::NT * u) * D + f] = v[u * D + f];
-            return;
-        }
-        if (tid < D * (G::H / 2)) { // halo: phase r, pair pi from the raw halo samples
-            const int r = tid / (G::H / 2), pi = tid % (G::H / 2);
-            const int sr = r == 0 ? 0 : D - r;
-            const int pa = D * (2 * pi) + sr, pb = D * (2 * pi + 1) + sr;
-            const float2 a = f4_sample(hsrc[pa >> 1], pa & 1), bb = f4_sample(hsrc[pb >> 1], pb & 1);
-            store_pair11<D, QH>(buf, r, 2 * pi, a.x, bb.x, a.y, bb.y, sc);
-        }
-#pragma unroll
-        for (int u = 0; u < G::UNITS; ++u) {
-            const int i0 = 2 * (tid + G::NT * u);
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                const int sr = r == 0 ? 0 : D - r;
-                const int la = sr, lb = D + sr;
-                const float2 a = f4_sample(v[u * D + la / 2], la & 1);
-                const float2 bb = f4_sample(v[u * D + lb / 2], lb & 1);
-                store_pair11<D, QH>(buf, r, G::H + i0, a.x, bb.x, a.y, bb.y, sc);
-            }
-        }
-    };
-    auto reduce = [&](const float4 (&v)[4], unsigned& m, unsigned& z) {
-        float mf = 0.f;
-        z = ~0u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            mf = __builtin_elementwise_maximum(mf, max_abs4(v[u]));
-            z = min(z, min_nz1(v[u]));
-        }
-        m = __float_as_uint(mf);
-        m = wave_max(m);
-        z = wave_min(z);
-    };
-    auto mfma_tile = [&](const unsigned char* cur, int unscale, nf2 (&o)[2 * G::TILES]) {
-        f32x4 hi[G::TILES], lo[G::TILES], hi_t[G::TILES], lo_t[G::TILES];
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-            hi[t] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-            lo[t] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-            hi_t[t] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-            lo_t[t] = f32x4{ 0.f, 0.f, 0.f, 0.f };
-        }
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-            const unsigned char* ph = cur + r * G::PH;
-#pragma unroll
-            for (int st = 0; st < KS; ++st) {
-                const int q = 2 * st + (g >> 1);
-#pragma unroll
-                for (int t = 0; t < G::TILES; ++t) {
-                    const int off = row_base + t * 8 * 32 - q * 32 + (g & 1) * 16;
-                    const f16x8 A0 = *reinterpret_cast<const f16x8*>(ph + off);
-                    const f16x8 A1 = *reinterpret_cast<const f16x8*>(ph + off + G::PLANE);
-                    hi[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0[r][st], hi[t], 0, 0, 0);
-                    lo[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1[r][st], lo[t], 0, 0, 0);
-                    lo[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0[r][st], lo[t], 0, 0, 0);
-                }
-            }
-            if constexpr (G::TAIL) { // separate accumulators: see v5_compute
-                // single ds_read_b64 (the empty asm keeps the compiler from pairing the tiles'
-                // reads into ds_read2_b64, whose 16-lane groups see the re and im rows 4 apart on
-                // one bank: 4-way, 43-50 % of the kernel's LDS cycles in profiles/r03o_pmc_decim.json;
-                // as ds_read_b64, 2-way)
-#pragma unroll
-                for (int t = 0; t < G::TILES; ++t) {
-                    const int off = row_base + t * 8 * 32 - (QH - 1) * 32 + g * 8;
-                    const f16x4 A0 = *reinterpret_cast<const f16x4*>(ph + off);
-                    asm volatile("" ::: "memory");
-                    const f16x4 A1 = *reinterpret_cast<const f16x4*>(ph + off + G::PLANE);
-                    asm volatile("" ::: "memory");
-                    hi_t[t] = __builtin_amdgcn_mfma_f32_16x16x16f16(A0, T0[r], hi_t[t], 0, 0, 0);
-                    lo_t[t] = __builtin_amdgcn_mfma_f32_16x16x16f16(A0, T1[r], lo_t[t], 0, 0, 0);
-                    lo_t[t] = __builtin_amdgcn_mfma_f32_16x16x16f16(A1, T0[r], lo_t[t], 0, 0, 0);
-                }
-            }
-        }
-        nf2 sum[2 * G::TILES];
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t)
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-                sum[2 * t + half] = (nf2{ hi[t][2 * half], hi[t][2 * half + 1] } + nf2{ hi_t[t][2 * half], hi_t[t][2 * half + 1] }) +
-                                    (nf2{ lo[t][2 * half], lo[t][2 * half + 1] } + nf2{ lo_t[t][2 * half], lo_t[t][2 * half + 1] });
-        unscale_tile(sum, unscale, o);
-    };
-    // exact path: y[m] = sum_k h[k] x[D m - k] from the raw chunk (float2 index D H + D m - k)
-    // exact path. D = 4: outputs 0 and 1 are 64 input samples apart and share their inputs
-    // (direct_group; decim_qh gives L - 1 <= D H and every k <= D (H - 16) below L): dense-exact
-    // floor 74.7 -> 97.6 GS/s input. D = 2 keeps one output at a time: its two unrolled groups
-    // cost the main path a third of its speed (594 -> 890 us per 2^28, profiles/r02o_*).
-    auto direct_tile = [&](const unsigned char* cur, nf2 (&o)[2 * G::TILES]) {
-        if constexpr (D == 4 || NSH_DECIM2_SHARED) {
-#pragma unroll 1
-            for (int t = 0; t < G::TILES; ++t) {
-                nf2 acc[2];
-                direct_group<2, 16 * D, D * G::H, D * (G::H - 16)>(
-                    reinterpret_cast<const nf2*>(cur), D * G::H + D * (wave * G::WAVE_OUT + (8 * t + 2 * g) * 16 + phase), taps, L, acc);
-                if (t == 0) {
-                    o[0] = acc[0];
-                    o[1] = acc[1];
-                } else {
-                    o[2 * G::TILES - 2] = acc[0];
-                    o[2 * G::TILES - 1] = acc[1];
-                }
-            }
-        } else {
-            const float2* raw = reinterpret_cast<const float2*>(cur);
-            for (int oi = 0; oi < 2 * G::TILES; ++oi) {
-                const int blk = (oi >> 1) * 8 + 2 * g + (oi & 1);
-                const int j = D * G::H + D * (wave * G::WAVE_OUT + blk * 16 + phase);
-                float re = 0.f, im = 0.f;
-                for (int k = 0; k < L; ++k) {
-                    const float2 x = raw[j - k];
-                    re = fmaf(taps[k], x.x, re);
-                    im = fmaf(taps[k], x.y, im);
-                }
-                o[oi] = nf2{ re, im };
-            }
-        }
-    };
-    // the tile's outputs n = 16 (32 wave + 8 t + 2 g + u) + i (undecimated), the lanes with
-    // i mod D = 0 keeping theirs (m = n / D), through the wave's LDS scratch into the split
-    // path's lane map (the wave's own outputs: a wave barrier, no workgroup barrier)
-    auto f32_tile = [&](const unsigned char* cur, nf2 (&o)[2 * G::TILES]) {
-        f32x4 acc[4];
-        nsh_f32t::tile_at<GF, G::QF>(cur, lds + G::TAPF, wave, lane, acc);
-        nf2* scr = reinterpret_cast<nf2*>(lds + G::SCR) + wave * G::WAVE_OUT;
-        const int i = lane & 15;
-        if (i % D == 0) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) scr[(16 * (8 * t + 2 * g + u) + i) / D] = nf2{ acc[t][2 * u], acc[t][2 * u + 1] };
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int oi = 0; oi < 2 * G::TILES; ++oi) o[oi] = scr[((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + phase];
-    };
-    auto store_tile = [&](int64_t ch, const nf2 (&o)[2 * G::TILES]) {
-        const __amdgpu_buffer_rsrc_t r = chunk_rsrc<G::CHUNK>(out, ch, n_out);
-#pragma unroll
-        for (int oi = 0; oi < 2 * G::TILES; ++oi)
-            buf_store_f2(r, (wave * G::WAVE_OUT + ((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + phase) * 8, o[oi]);
+        auto q_of = [&](int u, int f) { return (tid + G::NT * u) * D + f; }; // load's float4
+        if (__builtin_expect(f32t, 0))
+            stage_exact11<D, QH>(tid, buf, hsrc + tid, v, true, q_of);
+        else if (raw)
+            stage_exact11<D, QH>(tid, buf, hsrc + tid, v, false, q_of);
+        else
+            put_split11<D, QH, false>(tid, buf, hsrc, v, sc);
     };
 
     // ---- prologue: chunk c_begin's halo (global memory / history) into stash[1] (free until
@@ -759,7 +731,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
     load(va, c_begin);
     {
         unsigned m, z;
-        reduce(va, m, z);
+        wave_range(va, 0.f, ~0u, m, z);
         m = max(m, wave_max(max_mag(hv)));
         z = min(z, wave_min(min_nz1(hv)));
         if (lane == 0) {
@@ -768,8 +740,8 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
         }
     }
     nsh::lds_barrier();
-    unsigned m_prev = max(max(slot_max[0], slot_max[1]), max(slot_max[2], slot_max[3]));
-    unsigned z_prev = min(min(slot_mnz[0], slot_mnz[1]), min(slot_mnz[2], slot_mnz[3]));
+    unsigned m_prev = slots_max(slot_max);
+    unsigned z_prev = slots_min(slot_mnz);
     int s_cur = scale_of(m_prev);
     bool ex_cur = chunk_needs_exact(m_prev, z_prev, s_cur);
     bool f32_cur = ex_cur && m_prev < 0x7f800000u; // finite: the exact-fp32 tile
@@ -779,7 +751,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
     load(vb, clamp(c_begin + 2));
     {
         unsigned m, z;
-        reduce(va, m, z);
+        wave_range(va, 0.f, ~0u, m, z);
         nsh::lds_barrier(); // slots [0..3] and stash[1] read above
         if (lane == 0) {
             slot_max[4 + wave] = m;
@@ -793,8 +765,8 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
         const int pi = i & 1, pn = pi ^ 1;
         const unsigned char* cur = lds + pi * G::BUF;
         unsigned char* nbuf = lds + pn * G::BUF;
-        const unsigned m_nxt = max(max(slot_max[4 * pn], slot_max[4 * pn + 1]), max(slot_max[4 * pn + 2], slot_max[4 * pn + 3]));
-        const unsigned z_nxt = min(min(slot_mnz[4 * pn], slot_mnz[4 * pn + 1]), min(slot_mnz[4 * pn + 2], slot_mnz[4 * pn + 3]));
+        const unsigned m_nxt = slots_max(slot_max + 4 * pn);
+        const unsigned z_nxt = slots_min(slot_mnz + 4 * pn);
         const unsigned m2 = max(m_prev, m_nxt);
         const int s_nxt = scale_of(m2);
         const bool ex_nxt = chunk_needs_exact(m2, min(z_prev, z_nxt), s_nxt);
@@ -805,15 +777,15 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
         nf2 o[2 * G::TILES];
         if (__builtin_expect(ex_cur, 0)) {
             if (f32_cur)
-                f32_tile(cur, o);
+                f32_tile11<D, QH>(cur, lds, ln, o);
             else
-                direct_tile(cur, o);
+                direct_tile11<D, QH>(cur, taps, L, ln, o);
         } else {
-            mfma_tile(cur, -(s_cur + sh), o);
+            mfma_tile11<D, QH>(cur, ln, B0, B1, T0, T1, -(s_cur + sh), o);
         }
-        store_tile(ch, o);
+        store_tile11<D, QH>(out, ch, n_out, ln, o);
         unsigned m, z;
-        reduce(nn, m, z);
+        wave_range(nn, 0.f, ~0u, m, z);
         if (lane == 0) {
             slot_max[4 * pi + wave] = m;
             slot_mnz[4 * pi + wave] = z;
@@ -852,13 +824,6 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
 // them to the launch's exact queue and k_fir_exact13 (same stream, right after) filters them -- so a
 // periodic pattern of exact chunks, which the lockstep walk would put on one workgroup per XCD,
 // cannot unbalance it (r04zw: every 64th chunk exact 968 vs 548 us with the exact forms inline).
-// the chunk's float4 (2 input samples) a lane loads as its unit u, instruction f: the wave's
-// 64 D float4 of unit u in D contiguous 1 KiB runs
-template <int D>
-__device__ __forceinline__ int q13(int u, int f)
-{
-    return 64 * D * ((int)(threadIdx.x >> 6) + 4 * u) + 64 * f + (int)(threadIdx.x & 63);
-}
 template <int D, int QH>
 __device__ __forceinline__ void load13(const float2* __restrict__ in, const float2* __restrict__ hist_in, int L, int64_t n_in,
                                        int64_t ch, float4 (&v)[4], float4& hv)
@@ -876,28 +841,9 @@ __device__ __forceinline__ void load13(const float2* __restrict__ in, const floa
             const nsh::buf_f4 t = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, q * 16, 0, NSH_V13_AUX));
             v[u * D + f] = make_float4(t.x, t.y, t.z, t.w);
         }
-    // the halo: input samples [ch CHUNK_IN - 2 HP, ch CHUNK_IN), two per thread tid < HP, from `in`
-    // (ch > 0) or the history (ch = 0: element g + L - 1; out-of-range lanes and a null history read
-    // zeros); one buffer resource either way, no branch between the loads. A chunk index past the
-    // stream (an empty prefetch) reads zeros.
-    __amdgpu_buffer_rsrc_t hr;
-    int off0, off1;
-    if (ch > 0) {
-        hr = chunk_rsrc<2 * G::HP>(in + ch * G::CHUNK_IN - 2 * G::HP, 0, ch * G::CHUNK_IN <= n_in ? 2 * G::HP : 0);
-        off0 = 16 * tid;
-        off1 = off0 + 8;
-    } else {
-        hr = chunk_rsrc<1 << 20>(hist_in, 0, hist_in ? L - 1 : 0);
-        const int e = 2 * tid - 2 * G::HP + (L - 1);
-        off0 = e >= 0 ? 8 * e : 1 << 30;
-        off1 = e + 1 >= 0 ? 8 * (e + 1) : 1 << 30;
-    }
-    hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < G::HP) {
-        const nsh::buf_f2 a = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off0, 0, 0));
-        const nsh::buf_f2 b = __builtin_bit_cast(nsh::buf_f2, __builtin_amdgcn_raw_buffer_load_b64(hr, off1, 0, 0));
-        hv = make_float4(a.x, a.y, b.x, b.y);
-    }
+    // the halo: input samples [ch CHUNK_IN - 2 HP, ch CHUNK_IN); a chunk index past the stream (an
+    // empty prefetch) reads zeros
+    load_halo<2 * G::HP, G::CHUNK_IN, true>(in, hist_in, L, n_in, ch, tid, hv);
 }
 
 template <int D, int QH>
@@ -915,18 +861,16 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
 {
     using G = geom11<D, QH>;
     constexpr int KS = G::KS;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     float4* stash = reinterpret_cast<float4*>(lds + 2 * G::BUF); // [2][HP] raw halos, one step ahead
     unsigned* slot_max = reinterpret_cast<unsigned*>(lds + G::SLOTS);
     unsigned* slot_mnz = slot_max + 8;
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const lane11<D, QH> ln(tid);
+    const int lane = ln.lane, wave = ln.wave;
     const int64_t n_in = n_out * D;
-    if (blockIdx.x == 0)
-        for (int j = tid; j < L - 1; j += G::NT) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
+    if (blockIdx.x == 0) put_hist_tail<G::NT>(hist_out, in, hist_in, n_in, L);
 
     const int64_t nchunks = (n_out + G::CHUNK - 1) / G::CHUNK;
     const int W = (int)(gridDim.x >> 3);
@@ -953,74 +897,10 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
         T1[r] = tf[64 + lane];
     }
 
-    const int rho = lane & 15;
-    const int c = rho & 1, b = rho >> 1;
-    const int g = lane >> 4;
-    const int phase = lane & 15;
-    const int row_base = c * G::IM_OFF + (G::HR + wave * (G::WAVE_OUT / 16) + b) * 32;
-    auto reduce = [&](const float4 (&v)[4], const float4& hv, unsigned& m, unsigned& z) {
-        float mf = max_abs4(hv);
-        z = min_nz1(hv);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            mf = __builtin_elementwise_maximum(mf, max_abs4(v[u]));
-            z = min(z, min_nz1(v[u]));
-        }
-        m = wave_max(__float_as_uint(mf));
-        z = wave_min(z);
-    };
-    auto put_halo = [&](float4* st, const float4& hv) {
-        if (tid < G::HP) st[tid] = hv;
-    };
-    // chunk + its raw halo (stash) -> the split phase planes
-    auto put_split = [&](unsigned char* buf, const float4* hsrc, const float4 (&v)[4], int sc) {
-        if (tid < D * (G::H / 2)) { // halo: phase r, pair pi from the raw halo samples
-            const int r = tid / (G::H / 2), pi = tid % (G::H / 2);
-            const int sr = r == 0 ? 0 : D - r;
-            const int pa = D * (2 * pi) + sr, pb = D * (2 * pi + 1) + sr;
-            const float2 a = f4_sample(hsrc[pa >> 1], pa & 1), bb = f4_sample(hsrc[pb >> 1], pb & 1);
-            store_pair11<D, QH>(buf, r, 2 * pi, a.x, bb.x, a.y, bb.y, sc);
-        }
-#if NSH_V13_CLOAD
-        // float4 q holds samples 2q, 2q + 1: phase offsets 2q mod D (+1) at time 2q / D, the pair
-        // 2q / 2D, its time bit k = q & (D / 2). Lanes q and q ^ (D / 2) hold the same offsets at the
-        // pair's two times: each keeps offset k and takes the partner's (one DPP exchange per float),
-        // then stores one phase pair -- all D phases in each store instruction (PH padded for it)
-        constexpr int XCHG = D == 4 ? 0x4e : 0xb1; // quad_perm [2,3,0,1] / [1,0,3,2]: lane ^ (D / 2)
-#pragma unroll
-        for (int u = 0; u < G::UNITS; ++u)
-#pragma unroll
-            for (int f = 0; f < D; ++f) {
-                const int q = q13<D>(u, f);
-                const bool k = (q & (D / 2)) != 0;
-                const float4 x = v[u * D + f];
-                const float kre = k ? x.z : x.x, kim = k ? x.w : x.y; // offset k: kept
-                const float sre = k ? x.x : x.z, sim = k ? x.y : x.w; // offset 1 - k: the partner's
-                const float rre = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sre), XCHG, 0xf, 0xf, true));
-                const float rim = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sim), XCHG, 0xf, 0xf, true));
-                const int sr = D == 4 ? 2 * (q & 1) + (int)k : (int)k;
-                const int r = sr == 0 ? 0 : D - sr;
-                const int s = G::H + 2 * (q / D);
-                if (k)
-                    store_pair11<D, QH>(buf, r, s, rre, kre, rim, kim, sc);
-                else
-                    store_pair11<D, QH>(buf, r, s, kre, rre, kim, rim, sc);
-            }
-#else
-#pragma unroll
-        for (int u = 0; u < G::UNITS; ++u) {
-            const int i0 = 2 * (tid + G::NT * u);
-#pragma unroll
-            for (int r = 0; r < D; ++r) {
-                const int sr = r == 0 ? 0 : D - r;
-                const int la = sr, lb = D + sr;
-                const float2 a = f4_sample(v[u * D + la / 2], la & 1);
-                const float2 bb = f4_sample(v[u * D + lb / 2], lb & 1);
-                store_pair11<D, QH>(buf, r, G::H + i0, a.x, bb.x, a.y, bb.y, sc);
-            }
-        }
-#endif
-    };
+    // mfma_tile11, open-coded: through the helper k_fir_mfma13<4,3> (the benchmarked decimator) measured
+    // 0.2-1.3 % slower in every position of an interleaved three-library timing (2 more instructions,
+    // another schedule); k_fir_mfma11 calls the helper. Keep the two in step.
+    const int g = ln.g, row_base = ln.row_base;
     auto mfma_tile = [&](const unsigned char* cur, int unscale, nf2 (&o)[2 * G::TILES]) {
         f32x4 hi[G::TILES], lo[G::TILES], hi_t[G::TILES], lo_t[G::TILES];
 #pragma unroll
@@ -1046,7 +926,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
                     lo[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0[r][st], lo[t], 0, 0, 0);
                 }
             }
-            if constexpr (G::TAIL) { // separate accumulators, single ds_read_b64 (k_fir_mfma11)
+            if constexpr (G::TAIL) { // separate accumulators, single ds_read_b64 (mfma_tile11)
 #pragma unroll
                 for (int t = 0; t < G::TILES; ++t) {
                     const int off = row_base + t * 8 * 32 - (QH - 1) * 32 + g * 8;
@@ -1069,11 +949,8 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
                                     (nf2{ lo[t][2 * half], lo[t][2 * half + 1] } + nf2{ lo_t[t][2 * half], lo_t[t][2 * half + 1] });
         unscale_tile(sum, unscale, o);
     };
-    auto store_tile = [&](int64_t ch, const nf2 (&o)[2 * G::TILES]) {
-        const __amdgpu_buffer_rsrc_t r = chunk_rsrc<G::CHUNK>(out, ch, n_out);
-#pragma unroll
-        for (int oi = 0; oi < 2 * G::TILES; ++oi)
-            buf_store_f2(r, (wave * G::WAVE_OUT + ((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + phase) * 8, o[oi]);
+    auto put_halo = [&](float4* st, const float4& hv) {
+        if (tid < G::HP) st[tid] = hv;
     };
     // the workgroup's decision for a chunk from its slot set (SGPRs: scalar branches on it)
     struct decision {
@@ -1081,19 +958,11 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
         bool ex;
     };
     auto decide = [&](int par, int64_t ch) {
-        const unsigned m = __builtin_amdgcn_readfirstlane(
-            max(max(slot_max[4 * par], slot_max[4 * par + 1]), max(slot_max[4 * par + 2], slot_max[4 * par + 3])));
-        const unsigned z = __builtin_amdgcn_readfirstlane(
-            min(min(slot_mnz[4 * par], slot_mnz[4 * par + 1]), min(slot_mnz[4 * par + 2], slot_mnz[4 * par + 3])));
+        const unsigned m = __builtin_amdgcn_readfirstlane(slots_max(slot_max + 4 * par));
+        const unsigned z = __builtin_amdgcn_readfirstlane(slots_min(slot_mnz + 4 * par));
         const int s = scale_of(m);
         const bool ex = chunk_needs_exact(m, z, s);
-        if (ex && tid == 0 && ch < nchunks) { // to k_fir_exact13 (a vector atomic and a vector store from one lane)
-            const unsigned k = blockIdx.x % XQ_N;
-            const unsigned i = __hip_atomic_fetch_add(xq + XQ_LINE * k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (i < (unsigned)subcap)
-                __hip_atomic_store(xq + XQ_E + k * subcap + i, (unsigned)(ch << 1) | (m >= 0x7f800000u ? 1u : 0u),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (ex && tid == 0 && ch < nchunks) xq_append(xq, [&] { return subcap; }, ch, m); // to k_fir_exact13
         return decision{ s, ex };
     };
 
@@ -1103,7 +972,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
     load13<D, QH>(in, hist_in, L, n_in, chunk_at(0), va, ha);
     {
         unsigned m, z;
-        reduce(va, ha, m, z);
+        wave_range(va, max_abs4(ha), min_nz1(ha), m, z);
         put_halo(stash + G::HP, ha);
         if (lane == 0) {
             slot_max[wave] = m;
@@ -1112,12 +981,12 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
     }
     nsh::lds_barrier();
     decision d_cur = decide(0, chunk_at(0));
-    if (!d_cur.ex) put_split(lds, stash + G::HP, va, d_cur.s);
+    if (!d_cur.ex) put_split11<D, QH, NSH_V13_CLOAD>(tid, lds, stash + G::HP, va, d_cur.s);
     load13<D, QH>(in, hist_in, L, n_in, chunk_at(1), va, ha);
     load13<D, QH>(in, hist_in, L, n_in, chunk_at(2), vb, hb);
     {
         unsigned m, z;
-        reduce(va, ha, m, z);
+        wave_range(va, max_abs4(ha), min_nz1(ha), m, z);
         nsh::lds_barrier(); // slots [0..3] and stash[1] read above
         put_halo(stash, ha);
         if (lane == 0) {
@@ -1135,14 +1004,14 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
         unsigned char* nbuf = lds + pn * G::BUF;
         const decision d_nxt = decide(pn, chunk_at(i + 1));
         load13<D, QH>(in, hist_in, L, n_in, chunk_at(i + 3), ld, hld);
-        if (!d_nxt.ex) put_split(nbuf, stash + pi * G::HP, nxt, d_nxt.s);
+        if (!d_nxt.ex) put_split11<D, QH, NSH_V13_CLOAD>(tid, nbuf, stash + pi * G::HP, nxt, d_nxt.s);
         if (!d_cur.ex) {
             nf2 o[2 * G::TILES];
             mfma_tile(cur, -(d_cur.s + sh), o);
-            store_tile(chunk_at(i), o);
+            store_tile11<D, QH>(out, chunk_at(i), n_out, ln, o);
         }
         unsigned m, z;
-        reduce(nn, hnn, m, z);
+        wave_range(nn, max_abs4(hnn), min_nz1(hnn), m, z);
         put_halo(stash + pn * G::HP, hnn);
         if (lane == 0) {
             slot_max[4 * pi + wave] = m;
@@ -1181,109 +1050,32 @@ __global__ __launch_bounds__(256) void k_fir_exact13(const float2* __restrict__ 
     using GF = typename G::GF;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int g = lane >> 4;
-    const int phase = lane & 15;
-    if (blockIdx.x == 0 && tid < 64)
-        __hip_atomic_store(xq_next + XQ_LINE * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned incl = __hip_atomic_load(xq + XQ_LINE * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool over = __ballot(incl > (unsigned)subcap) != 0; // lost entries: every chunk again (k_fir_exact12)
-    incl = min(incl, (unsigned)subcap);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const unsigned cnt = over ? (unsigned)((n_out + G::CHUNK - 1) / G::CHUNK) : __builtin_amdgcn_readlane(incl, 63);
-    if (cnt == 0) return; // nothing queued (the common case)
-    auto entry = [&](unsigned i) {
-        if (over) return (i << 1) | 1u; // chunk i, direct form
-        const int k = __popcll(__ballot(incl <= i));
-        const unsigned start = k ? __shfl(incl, k - 1) : 0u;
-        return __hip_atomic_load(xq + XQ_E + k * subcap + (i - start), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    const lane11<D, QH> ln(tid);
+    const xq_reader q(xq, xq_next, subcap, n_out, G::CHUNK, tid);
+    if (q.cnt == 0) return; // nothing queued (the common case)
     {   // the tile's taps, once per workgroup (read after the first chunk's barrier)
         float4 t32[2];
         nsh_f32t::load_taps<GF>(timg32, t32, tid, G::NT);
         nsh_f32t::put_taps_at<GF>(lds + G::TAPF, t32, tid, G::NT);
     }
     const int64_t n_in = n_out * D;
-    const int64_t nchunks = (n_out + G::CHUNK - 1) / G::CHUNK;
-    for (unsigned i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const unsigned e = entry(i);
+    for (unsigned i = blockIdx.x; i < q.cnt; i += gridDim.x) {
+        const unsigned e = q.entry(i);
         const int64_t ch = (int64_t)(e >> 1);
-        if (ch >= nchunks) continue; // never for a queue this launch filled (defensive)
+        if (ch >= q.nchunks) continue; // never for a queue this launch filled (defensive)
         const bool f32t = !(e & 1u);
         float4 v[4], hv;
         load13<D, QH>(in, hist_in, L, n_in, ch, v, hv);
         auto q_of = [&](int u, int f) { return NSH_V13_CLOAD ? q13<D>(u, f) : (tid + G::NT * u) * D + f; }; // load13's float4
         nsh::lds_barrier(); // the previous chunk's reads of LDS are done
-        if (f32t) {
-            if (tid < G::HP) nsh_f32t::put<GF>(lds, hv, 2 * tid);
-#pragma unroll
-            for (int u = 0; u < G::UNITS; ++u)
-#pragma unroll
-                for (int f = 0; f < D; ++f) nsh_f32t::put<GF>(lds, v[u * D + f], GF::H + 2 * q_of(u, f));
-        } else {
-            float4* rb = reinterpret_cast<float4*>(lds);
-            if (tid < G::HP) rb[tid] = hv;
-#pragma unroll
-            for (int u = 0; u < G::UNITS; ++u)
-#pragma unroll
-                for (int f = 0; f < D; ++f) rb[G::HP + q_of(u, f)] = v[u * D + f];
-        }
+        stage_exact11<D, QH>(tid, lds, &hv, v, f32t, q_of);
         nsh::lds_barrier();
         nf2 o[2 * G::TILES];
-        if (f32t) {
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-            f32x4 acc[4];
-            nsh_f32t::tile_at<GF, G::QF>(lds, lds + G::TAPF, wave, lane, acc);
-            nf2* scr = reinterpret_cast<nf2*>(lds + G::SCR) + wave * G::WAVE_OUT;
-            const int ii = lane & 15;
-            if (ii % D == 0) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) scr[(16 * (8 * t + 2 * g + u) + ii) / D] = nf2{ acc[t][2 * u], acc[t][2 * u + 1] };
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int oi = 0; oi < 2 * G::TILES; ++oi) o[oi] = scr[((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + phase];
-        } else if constexpr (D == 4 || NSH_DECIM2_SHARED) {
-#pragma unroll 1
-            for (int t = 0; t < G::TILES; ++t) {
-                nf2 acc[2];
-                direct_group<2, 16 * D, D * G::H, D * (G::H - 16)>(
-                    reinterpret_cast<const nf2*>(lds), D * G::H + D * (wave * G::WAVE_OUT + (8 * t + 2 * g) * 16 + phase), taps, L, acc);
-                if (t == 0) {
-                    o[0] = acc[0];
-                    o[1] = acc[1];
-                } else {
-                    o[2 * G::TILES - 2] = acc[0];
-                    o[2 * G::TILES - 1] = acc[1];
-                }
-            }
-        } else {
-            const float2* raw = reinterpret_cast<const float2*>(lds);
-            for (int oi = 0; oi < 2 * G::TILES; ++oi) {
-                const int blk = (oi >> 1) * 8 + 2 * g + (oi & 1);
-                const int j = D * G::H + D * (wave * G::WAVE_OUT + blk * 16 + phase);
-                float re = 0.f, im = 0.f;
-                for (int k = 0; k < L; ++k) {
-                    const float2 x = raw[j - k];
-                    re = fmaf(taps[k], x.x, re);
-                    im = fmaf(taps[k], x.y, im);
-                }
-                o[oi] = nf2{ re, im };
-            }
-        }
-        const __amdgpu_buffer_rsrc_t r = chunk_rsrc<G::CHUNK>(out, ch, n_out);
-#pragma unroll
-        for (int oi = 0; oi < 2 * G::TILES; ++oi)
-            buf_store_f2(r, (wave * G::WAVE_OUT + ((oi >> 1) * 8 + 2 * g + (oi & 1)) * 16 + phase) * 8, o[oi]);
+        if (f32t)
+            f32_tile11<D, QH>(lds, lds, ln, o);
+        else
+            direct_tile11<D, QH>(lds, taps, L, ln, o);
+        store_tile11<D, QH>(out, ch, n_out, ln, o);
     }
 }
 
@@ -1341,6 +1133,36 @@ void xq_reset(const nsh_fir_plan* p, hipStream_t s)
         }
 }
 
+// A main kernel and its exact kernel on stream s, sharing one set of the plan's exact queue
+// (sub-queues of subcap entries): main(cur, start) launches the main kernel appending to set cur,
+// exact(cur, nxt, stop) the exact kernel draining it and zeroing set nxt. A timed call is timed as
+// one: start with the main kernel's dispatch, stop with the exact kernel's (the follow-up launch and
+// every exact chunk are inside the pair).
+template <class Main, class Exact>
+int launch_queued(const nsh_fir_plan* p, hipStream_t s, int64_t subcap, const char* what_queue, const char* what_main,
+                  const char* what_exact, Main main, Exact exact)
+{
+    hipError_t e;
+    int64_t stride = 0;
+    int set = 0;
+    unsigned* xq = exact_queue(p, s, XQ_E + XQ_N * subcap, stride, set, e);
+    if (!xq) return nsh::fail(e, what_queue);
+    unsigned* cur = xq + set * stride;
+    unsigned* nxt = xq + (set ^ 1) * stride;
+    const nsh::launch_events t = nsh::take_launch_events();
+    main(cur, t.start);
+    if ((e = hipGetLastError()) != hipSuccess) {
+        xq_reset(p, s);
+        return nsh::fail(e, what_main);
+    }
+    exact(cur, nxt, t.stop);
+    if ((e = hipGetLastError()) != hipSuccess) {
+        xq_reset(p, s);
+        return nsh::fail(e, what_exact);
+    }
+    return 0;
+}
+
 template <int D, int QH>
 int launch_v11(const nsh_fir_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out,
                hipStream_t s)
@@ -1378,29 +1200,19 @@ int launch_v13(const nsh_fir_plan* p, const float2* in, const float2* hin, float
     const int64_t grid = 8 * (int64_t)W;
     const int64_t steps = (per_x + W - 1) / W;
     const int64_t subcap = xq_subcap(grid) * steps; // a sub-queue's workgroups can queue every chunk they walk
-    hipError_t e;
-    int64_t stride = 0;
-    int set = 0;
-    unsigned* xq = exact_queue(p, s, XQ_E + XQ_N * subcap, stride, set, e);
-    if (!xq) return nsh::fail(e, "nsh_fir_ccf(mfma decim): exact queue");
-    unsigned* cur = xq + set * stride;
-    unsigned* nxt = xq + (set ^ 1) * stride;
-    const nsh::launch_events t = nsh::take_launch_events(); // one pair over both kernels
-    nsh::launch_timed((k_fir_mfma13<D, QH>), dim3((unsigned)grid), dim3(G::NT), G::LDS, s, t.start, (hipEvent_t) nullptr, in,
-                      hin, hout, out, (const _Float16*)p->fragd8_dev, cur, subcap, p->L, p->sh8, n_out, per_x);
-    if ((e = hipGetLastError()) != hipSuccess) {
-        xq_reset(p, s);
-        return nsh::fail(e, "nsh_fir_ccf(mfma decim v13)");
-    }
     const int64_t xcap = (int64_t)n_cu * NSH_X12_PER_CU;
-    nsh::launch_timed((k_fir_exact13<D, QH>), dim3((unsigned)(nchunks < xcap ? nchunks : xcap)), dim3(G::NT), GX::LDS, s,
-                      (hipEvent_t) nullptr, t.stop, in, hin, out, (const float4*)p->tf32q_dev, (const float*)p->taps_dev,
-                      (const unsigned*)cur, nxt, subcap, p->L, n_out);
-    if ((e = hipGetLastError()) != hipSuccess) {
-        xq_reset(p, s);
-        return nsh::fail(e, "nsh_fir_ccf(mfma decim v13 exact chunks)");
-    }
-    return 0;
+    return launch_queued(
+        p, s, subcap, "nsh_fir_ccf(mfma decim): exact queue", "nsh_fir_ccf(mfma decim v13)",
+        "nsh_fir_ccf(mfma decim v13 exact chunks)",
+        [&](unsigned* cur, hipEvent_t start) {
+            nsh::launch_timed((k_fir_mfma13<D, QH>), dim3((unsigned)grid), dim3(G::NT), G::LDS, s, start, (hipEvent_t) nullptr, in,
+                              hin, hout, out, (const _Float16*)p->fragd8_dev, cur, subcap, p->L, p->sh8, n_out, per_x);
+        },
+        [&](const unsigned* cur, unsigned* nxt, hipEvent_t stop) {
+            nsh::launch_timed((k_fir_exact13<D, QH>), dim3((unsigned)(nchunks < xcap ? nchunks : xcap)), dim3(G::NT), GX::LDS, s,
+                              (hipEvent_t) nullptr, stop, in, hin, out, (const float4*)p->tf32q_dev, (const float*)p->taps_dev,
+                              cur, nxt, subcap, p->L, n_out);
+        });
 }
 
 template <int D, int QH>
@@ -1436,32 +1248,19 @@ int launch_v12(const nsh_fir_plan* p, const float2* in, const float2* hin, float
     const int64_t per_x = (nchunks + 7) / 8; // workgroups (= chunks) per XCD
     const int64_t grid = per_x * 8;
     if (grid > 0x7fffffff) return nsh::fail_msg("nsh_fir_ccf(mfma v12): stream too long for one launch");
-    hipError_t e;
     const int64_t subcap = xq_subcap(grid);
-    int64_t stride = 0;
-    int set = 0;
-    unsigned* xq = exact_queue(p, s, XQ_E + XQ_N * subcap, stride, set, e);
-    if (!xq) return nsh::fail(e, "nsh_fir_ccf(mfma v12): exact queue");
-    unsigned* cur = xq + set * stride;
-    unsigned* nxt = xq + (set ^ 1) * stride;
-    // a timed call is timed as one: start with k_fir_mfma12's dispatch, stop with k_fir_exact12's
-    // (the follow-up launch and every exact chunk are inside the pair)
-    const nsh::launch_events t = nsh::take_launch_events();
-    nsh::launch_timed((k_fir_mfma12<Q>), dim3((unsigned)grid), dim3(G::NT), G::LDS, s, t.start, (hipEvent_t) nullptr, in,
-                      hin, hout, out, (const uint4*)p->frag12_dev, cur, p->L, p->sh8, n_out, per_x);
-    if ((e = hipGetLastError()) != hipSuccess) {
-        xq_reset(p, s);
-        return nsh::fail(e, "nsh_fir_ccf(mfma fp16x2 v12)");
-    }
     const int64_t xcap = (int64_t)plan_cus(p) * NSH_X12_PER_CU;
-    nsh::launch_timed((k_fir_exact12<Q>), dim3((unsigned)(nchunks < xcap ? nchunks : xcap)), dim3(G::NT), G::LDS, s,
-                      (hipEvent_t) nullptr, t.stop, in, hin, out, (const float4*)p->tf32q_dev, (const float*)p->taps_dev,
-                      (const unsigned*)cur, nxt, subcap, p->L, n_out);
-    if ((e = hipGetLastError()) != hipSuccess) {
-        xq_reset(p, s);
-        return nsh::fail(e, "nsh_fir_ccf(mfma v12 exact chunks)");
-    }
-    return 0;
+    return launch_queued(
+        p, s, subcap, "nsh_fir_ccf(mfma v12): exact queue", "nsh_fir_ccf(mfma fp16x2 v12)", "nsh_fir_ccf(mfma v12 exact chunks)",
+        [&](unsigned* cur, hipEvent_t start) {
+            nsh::launch_timed((k_fir_mfma12<Q>), dim3((unsigned)grid), dim3(G::NT), G::LDS, s, start, (hipEvent_t) nullptr, in, hin,
+                              hout, out, (const uint4*)p->frag12_dev, cur, p->L, p->sh8, n_out, per_x);
+        },
+        [&](const unsigned* cur, unsigned* nxt, hipEvent_t stop) {
+            nsh::launch_timed((k_fir_exact12<Q>), dim3((unsigned)(nchunks < xcap ? nchunks : xcap)), dim3(G::NT), G::LDS, s,
+                              (hipEvent_t) nullptr, stop, in, hin, out, (const float4*)p->tf32q_dev, (const float*)p->taps_dev, cur,
+                              nxt, subcap, p->L, n_out);
+        });
 }
 
 
@@ -1516,22 +1315,10 @@ int nsh_fir_mfma_prepare_decim(nsh_fir_plan* p)
     // k_fir_mfma11: the same polyphase taps scaled by 2^sh8 (max |h| * 2^sh8 in [2^14, 2^15),
     // as for decim 1) and split into two fp16 terms; per phase [2][KS][64] x8 then [2][64] x4
     {
-        unsigned maxbits = 0;
-        for (float t : p->taps_host) {
-            unsigned u;
-            std::memcpy(&u, &t, 4);
-            maxbits = std::max(maxbits, u & 0x7fffffffu);
-        }
-        const int sh = 141 - (int)(maxbits >> 23);
-        p->sh8 = sh;
+        const int sh = p->sh8 = tap_scale(p);
         const size_t pp = (size_t)2 * KS * 64 * 8 + (size_t)2 * 64 * 4;
         std::vector<_Float16> f8((size_t)D * pp, (_Float16)0.f);
-        auto put2 = [&](float hv, size_t i0, size_t i1) {
-            const float hs = std::ldexp(hv, sh);
-            const _Float16 h0 = (_Float16)hs;
-            f8[i0] = h0;
-            f8[i1] = (_Float16)(hs - (float)h0);
-        };
+        auto put2 = [&](float hv, size_t i0, size_t i1) { split_tap(hv, sh, f8[i0], f8[i1]); };
         for (int r = 0; r < D; ++r) {
             const size_t base = (size_t)r * pp;
             for (int st = 0; st < KS; ++st)
@@ -1567,28 +1354,19 @@ int nsh_fir_mfma_prepare(nsh_fir_plan* p)
     // subnormal range or flushes: it is then exact to 2^-39 of the largest tap, which moves an
     // output by at most 2^-39 max|h| sum|x|, far below fp32's own rounding of the sum. So every
     // finite tap set qualifies.
-    unsigned maxbits = 0;
-    for (float t : p->taps_host) {
-        unsigned u;
-        std::memcpy(&u, &t, 4);
-        maxbits = std::max(maxbits, u & 0x7fffffffu);
-    }
-    const int sh = 141 - (int)(maxbits >> 23);
-    p->sh8 = sh;
+    const int sh = p->sh8 = tap_scale(p);
     {
-            // v12 tap image: R[m] = h[32Q - 1 - m] (scaled, hi/lo fp16), copy k holds R[k .. k + TW)
-            const int TW = v12_tw(Q), NCP = NSH_V12_COPIES;
-            std::vector<_Float16> f12((size_t)2 * NCP * TW, (_Float16)0.f);
-            for (int k = 0; k < NCP; ++k)
-                for (int e = 0; e < TW; ++e) {
-                    const int t = 32 * Q - 1 - (e + k);
-                    const float hs = (t >= 0 && t < p->L) ? std::ldexp(p->taps_host[t], sh) : 0.f;
-                    const _Float16 h0 = (_Float16)hs;
-                    f12[(size_t)(0 * NCP + k) * TW + e] = h0;
-                    f12[(size_t)(1 * NCP + k) * TW + e] = (_Float16)(hs - (float)h0);
-                }
-            NSH_CK(hipMalloc(&p->frag12_dev, f12.size() * sizeof(_Float16)));
-            NSH_CK(hipMemcpy(p->frag12_dev, f12.data(), f12.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        // v12 tap image: R[m] = h[32Q - 1 - m] (scaled, hi/lo fp16), copy k holds R[k .. k + TW)
+        const int TW = v12_tw(Q), NCP = NSH_V12_COPIES;
+        std::vector<_Float16> f12((size_t)2 * NCP * TW, (_Float16)0.f);
+        for (int k = 0; k < NCP; ++k)
+            for (int e = 0; e < TW; ++e) {
+                const int t = 32 * Q - 1 - (e + k);
+                split_tap((t >= 0 && t < p->L) ? p->taps_host[t] : 0.f, sh, f12[(size_t)(0 * NCP + k) * TW + e],
+                          f12[(size_t)(1 * NCP + k) * TW + e]);
+            }
+        NSH_CK(hipMalloc(&p->frag12_dev, f12.size() * sizeof(_Float16)));
+        NSH_CK(hipMemcpy(p->frag12_dev, f12.data(), f12.size() * sizeof(_Float16), hipMemcpyHostToDevice));
     }
     NSH_CK(f32_tile_image(p, 2 * Q - 1)); // k_fir_mfma12's tile: v12's 32 (Q - 1)-sample halo
     return 0;

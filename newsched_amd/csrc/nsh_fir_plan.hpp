@@ -19,7 +19,7 @@ struct nsh_fir_plan {
     int Q = 0;
     int S = 0;
     void* frag12_dev = nullptr;
-    // decimating polyphase form (k_fir_mfma11, D = 2, 4): per phase QHD tap blocks of 16, fp16x2
+    // decimating polyphase form (k_fir_mfma13 / k_fir_mfma11, D = 2, 4): per phase QHD tap blocks of 16, fp16x2
     // fragments [phase][part(2)][kstep][lane][8] + [phase][part][lane][4] tail, taps scaled by 2^sh8
     int QHD = 0;
     void* fragd8_dev = nullptr;
@@ -28,8 +28,8 @@ struct nsh_fir_plan {
     // as 4 shifted copies [4][16 QF + 16] fp32
     int QF = 0;
     void* tf32_dev = nullptr;
-    void* tf32q_dev = nullptr; // the exact-fp32 tile taps of k_fir_mfma12 / k_fir_mfma11, same layout
-    int QFT = 0;               // their tap blocks: 2Q - 1 (k_fir_mfma12), D (QHD - 1) + 1 (k_fir_mfma11)
+    void* tf32q_dev = nullptr; // the exact-fp32 tile taps of k_fir_exact12 / k_fir_exact13 / k_fir_mfma11, same layout
+    int QFT = 0;               // their tap blocks: 2Q - 1 (decim 1), D (QHD - 1) + 1 (decim 2, 4)
     // k_fir_mfma12's exact queue, one per stream the plan runs on (the chunks it hands to
     // k_fir_exact12: device words [count, done, entries...], nsh_fir_mfma.hip); launches on one
     // stream are ordered, so each stream's queue is empty again when its next launch starts
