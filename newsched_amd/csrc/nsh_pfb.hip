@@ -343,7 +343,7 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
             host[ntap + 2 * ((size_t)s * M + q) + 1] = (float)sn;
         }
     }
-    // at most 37.5 KiB (M = 64 with 1024 taps)
+    // at most 37.75 KiB (38 656 bytes, M = 32 with 1024 taps; M = 64 with 1024 taps: 38 400)
     hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
     if (e == hipSuccess) e = hipMalloc(&p->hp_dev, host.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(p->hp_dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
