@@ -137,18 +137,36 @@ struct geom12 {
     static_assert(IMG_UNITS <= 2 * NT, "tap image: two 16-B units per thread at most");
 };
 
-template <int Q>
-__device__ __forceinline__ void store_pair12(const float4& v, unsigned char* buf, int s, int sc)
+// two adjacent samples (v, as loaded) scaled by 2^sc and split -> the four planes at p (the pair's
+// place in plane 0): two packed multiplies (MUL: scale2), two v_cvt_pk_f16_f32 and four
+// v_fma_mix*_f16 per float4 (split_pair16)
+template <int Q, bool MUL>
+__device__ __forceinline__ void store_pair12(const float4& v, unsigned char* p, int sc)
 {
     using G = geom12<Q>;
-    const int off = G::at(s);
+    const nf2 a = scale2<MUL>(v.x, v.y, sc), b = scale2<MUL>(v.z, v.w, sc);
     unsigned rh, rl, ih, il;
-    split_pair16(v.x, v.z, sc, rh, rl);
-    split_pair16(v.y, v.w, sc, ih, il);
-    *reinterpret_cast<unsigned*>(buf + 0 * G::PLANE + off) = rh;
-    *reinterpret_cast<unsigned*>(buf + 1 * G::PLANE + off) = rl;
-    *reinterpret_cast<unsigned*>(buf + 2 * G::PLANE + off) = ih;
-    *reinterpret_cast<unsigned*>(buf + 3 * G::PLANE + off) = il;
+    split_pair16(a.x, b.x, rh, rl);
+    split_pair16(a.y, b.y, ih, il);
+    *reinterpret_cast<unsigned*>(p + 0 * G::PLANE) = rh;
+    *reinterpret_cast<unsigned*>(p + 1 * G::PLANE) = rl;
+    *reinterpret_cast<unsigned*>(p + 2 * G::PLANE) = ih;
+    *reinterpret_cast<unsigned*>(p + 3 * G::PLANE) = il;
+}
+// The chunk (v: lane t holds samples (2t, 2t + 1) + 512 u) and its halo pair hv (tid < HP) -> the
+// split planes. One address per thread: sample H + 2 (tid + 256 u) lies 16 u rows below sample
+// H + 2 tid in the same column, so at the 80-B pitch unit u is stored at the thread's base plus
+// the constant 1280 u (= 5 x 256: with the planes a multiple of 256 B apart, every store of the
+// thread is an immediate of one ds_write2st64_b32 base). The swizzled 64-B pitch keeps at().
+template <int Q, bool MUL>
+__device__ __forceinline__ void split_chunk12(unsigned char* lds, const float4 (&v)[4], const float4& hv, int tid, int sc)
+{
+    using G = geom12<Q>;
+    if (tid < G::HP) store_pair12<Q, MUL>(hv, lds + G::at(2 * tid), sc);
+    unsigned char* base = lds + G::at(G::H + 2 * tid);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        store_pair12<Q, MUL>(v[u], G::PITCH == 80 ? base + 16 * 80 * u : lds + G::at(G::H + 2 * (tid + G::NT * u)), sc);
 }
 
 // Chunks the split cannot carry leave the bench kernel (round 4, verdict r03 item 4). A chunk
@@ -422,43 +440,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     if (__builtin_expect(chunk_needs_exact(m, z, s), 0)) {
         if (tid == 0) xq_append(xq, [] { return xq_subcap(gridDim.x); }, ch, m); // k_fir_exact12 filters it
     } else {
-        if (tid < G::HP) store_pair12<Q>(hv, lds, 2 * tid, s);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) store_pair12<Q>(v[u], lds, G::H + 2 * (tid + G::NT * u), s);
+        if (__builtin_expect(scale_is_mul(s), 1)) // the scale's form, once per chunk (s is in an SGPR)
+            split_chunk12<Q, true>(lds, v, hv, tid, s);
+        else
+            split_chunk12<Q, false>(lds, v, hv, tid, s);
         nsh::lds_barrier();
+        // Fragment addresses: one base per thread for A and one for B, taken at the k-step with the
+        // lowest address (the last row pair, st >> 1 = Q - 1, first half), every step a compile-time
+        // offset from it -- DS immediates are unsigned -- so the loop holds only LDS reads and MFMAs.
         const int b = rho & 15, c = rho >> 4;
         const int row0 = (Q - 1) + 16 * wave + b; // A rows: row0 - (st >> 1); chunks h + 2 (st & 1)
-        const int a_base = c * 2 * G::PLANE + row0 * G::PITCH + 16 * h;
+        const unsigned char* a_lo = lds + c * 2 * G::PLANE + (16 * wave + b) * G::PITCH + 16 * h;
+        // taps h[t0 - j], t0 = i - 16 (st & 1) - 8 h + 32 (st >> 1): R[m0 + j], m0 = 32Q - 1 - t0 =
+        // m_lo + 16 (st & 1) + 32 (Q - 1 - (st >> 1)) with m_lo = 31 - rho + 8 h >= 0. Every step moves
+        // m0 by a multiple of 8, so the copy (m0 mod NCP) is the thread's own and only the element
+        // offset moves: 2 bytes per tap.
+        const int m_lo = 31 - rho + 8 * h;
+        const unsigned char* t_lo = tl + (m_lo & (G::NCP - 1)) * G::COPY + 2 * (m_lo & ~(G::NCP - 1));
         f32x16 acc_hi = {};
         f32x16 acc_lo = {};
 #pragma unroll
         for (int st = 0; st < 2 * Q; ++st) {
-            int off;
+            const int up = (Q - 1) - (st >> 1); // row pairs above the lowest
+            const unsigned char* ap;
             if (G::PITCH == 80) {
-                off = a_base - (st >> 1) * 80 + 32 * (st & 1);
+                ap = a_lo + 80 * up + 32 * (st & 1);
             } else {
                 const int row = row0 - (st >> 1);
-                off = c * 2 * G::PLANE + row * 64 + (((h + 2 * (st & 1)) ^ ((row >> 2) & 3)) << 4);
+                ap = lds + c * 2 * G::PLANE + row * 64 + (((h + 2 * (st & 1)) ^ ((row >> 2) & 3)) << 4);
             }
-            const f16x8 A0 = *reinterpret_cast<const f16x8*>(lds + off);
-            const f16x8 A1 = *reinterpret_cast<const f16x8*>(lds + off + G::PLANE);
-            // taps h[t0 - j], t0 = i - 16 (st & 1) - 8 h + 32 (st >> 1): R[m0 + j], m0 = 32Q - 1 - t0
-            const int m0 = 32 * Q - 1 - rho + 16 * (st & 1) + 8 * h - 32 * (st >> 1);
-            const int tb = (m0 & (G::NCP - 1)) * G::COPY + 2 * (m0 & ~(G::NCP - 1));
+            const f16x8 A0 = *reinterpret_cast<const f16x8*>(ap);
+            const f16x8 A1 = *reinterpret_cast<const f16x8*>(ap + G::PLANE);
+            const unsigned char* tp = t_lo + 2 * (16 * (st & 1) + 32 * up);
             f16x8 B0, B1;
             if (G::NCP == 8) {
-                B0 = *reinterpret_cast<const f16x8*>(tl + tb);
-                B1 = *reinterpret_cast<const f16x8*>(tl + G::NCP * G::COPY + tb);
+                B0 = *reinterpret_cast<const f16x8*>(tp);
+                B1 = *reinterpret_cast<const f16x8*>(tp + G::NCP * G::COPY);
             } else {
                 // four separate ds_read_b64 (the empty asm keeps the compiler from pairing
                 // them into ds_read2_b64, whose 16-lane groups conflict 2-way on this image)
-                const f16x4 b0 = *reinterpret_cast<const f16x4*>(tl + tb);
+                const f16x4 b0 = *reinterpret_cast<const f16x4*>(tp);
                 asm volatile("" ::: "memory");
-                const f16x4 b1 = *reinterpret_cast<const f16x4*>(tl + tb + 8);
+                const f16x4 b1 = *reinterpret_cast<const f16x4*>(tp + 8);
                 asm volatile("" ::: "memory");
-                const f16x4 b2 = *reinterpret_cast<const f16x4*>(tl + G::NCP * G::COPY + tb);
+                const f16x4 b2 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY);
                 asm volatile("" ::: "memory");
-                const f16x4 b3 = *reinterpret_cast<const f16x4*>(tl + G::NCP * G::COPY + tb + 8);
+                const f16x4 b3 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY + 8);
+                asm volatile("" ::: "memory"); // nor with the next step's: all steps read off one base now
                 B0 = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                 B1 = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
             }

@@ -59,16 +59,40 @@ typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-// fp16x2 split of the pair (a, b) * 2^sc: hi = RNE fp16 of each, lo = RNE fp16 of the exact
-// residuals. As packed vectors: one v_cvt_pk_f16_f32 per plane, the residual as one packed
-// subtract (the scalar form converted every value twice).
-__device__ __forceinline__ void split_pair16(float a, float b, int sc, unsigned& hi, unsigned& lo)
+// A chunk's scale 2^sc applied to two adjacent samples' components (a register pair as loaded).
+// MUL: one packed multiply by 2^sc, a normal float for sc in [-126, 127] -- a multiply by a power of
+// two rounds exactly as ldexp does. scale_of gives sc >= -113 for finite chunks and up to 141 for
+// chunks whose largest magnitude is below 2^-113: those (sc > 127) keep ldexp. The choice is
+// workgroup-uniform: the kernels branch on scale_is_mul once per chunk, around all its split stores
+// (as unscale_tile does on the output side).
+__device__ __forceinline__ bool scale_is_mul(int sc) { return sc <= 127; }
+template <bool MUL>
+__device__ __forceinline__ nf2 scale2(float a, float b, int sc)
 {
-    const f32x2 x = f32x2{ __builtin_ldexpf(a, sc), __builtin_ldexpf(b, sc) };
-    const f16x2 h = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(h, f32x2);
+    if (MUL) return nf2{ a, b } * __builtin_bit_cast(float, (sc + 127) << 23);
+    return nf2{ __builtin_ldexpf(a, sc), __builtin_ldexpf(b, sc) };
+}
+// fp16x2 split of the scaled pair (a, b): hi = RNE fp16 of each (one v_cvt_pk_f16_f32), lo = RNE
+// fp16 of the exact residuals a - hi.a, b - hi.b. The residual has at most 13 significant bits, so
+// it is exact in fp32 and fp16(fma(a, 1, -hi.a)) rounds once, to the same value as the subtract
+// followed by a conversion: one v_fma_mix{lo,hi}_f16 per value, reading the fp32 sample and its
+// half of the packed hi word, in place of two v_cvt_f32_f16, a v_pk_add_f32 and a
+// v_cvt_pk_f16_f32 per pair. The compiler does not form it from C++ (it folds fma(-hi, 1, a) back
+// to the subtract): inline asm; NSH_SPLIT_FMA_MIX=0 builds the C++ form (probe builds compare the two).
+#ifndef NSH_SPLIT_FMA_MIX
+#define NSH_SPLIT_FMA_MIX 1
+#endif
+__device__ __forceinline__ void split_pair16(float a, float b, unsigned& hi, unsigned& lo)
+{
+    const f16x2 h = __builtin_convertvector(f32x2{ a, b }, f16x2);
     hi = __builtin_bit_cast(unsigned, h);
+#if NSH_SPLIT_FMA_MIX
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(a), "v"(hi));
+    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(b), "v"(hi));
+#else
+    const f32x2 r = f32x2{ a, b } - __builtin_convertvector(h, f32x2);
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
+#endif
 }
 
 // largest magnitude as a bit pattern: NaN-propagating v_maximum3_f32 with |.| operand modifiers
@@ -254,15 +278,15 @@ struct geom11 {
     static_assert(HP <= NT && H / 2 <= NT, "halo: one float4 per thread");
 };
 
+// the pair of scaled samples a, b (time s, s + 1 of phase r) -> the phase's four planes
 template <class G>
-__device__ __forceinline__ void store_pair_g(unsigned char* buf, int r, int s, float a_re, float b_re, float a_im,
-                                             float b_im, int sc)
+__device__ __forceinline__ void store_pair_g(unsigned char* buf, int r, int s, nf2 a, nf2 b)
 {
     unsigned char* ph = buf + r * G::PH;
     const int off = (s >> 4) * 32 + (s & 15) * 2;
     unsigned rh, rl, ih, il;
-    split_pair16(a_re, b_re, sc, rh, rl);
-    split_pair16(a_im, b_im, sc, ih, il);
+    split_pair16(a.x, b.x, rh, rl);
+    split_pair16(a.y, b.y, ih, il);
     *reinterpret_cast<unsigned*>(ph + off) = rh;
     *reinterpret_cast<unsigned*>(ph + G::PLANE + off) = rl;
     *reinterpret_cast<unsigned*>(ph + G::IM_OFF + off) = ih;
@@ -283,10 +307,9 @@ __device__ __forceinline__ void unscale_tile(const nf2 (&s)[M], int u, nf2 (&o)[
     }
 }
 template <int D, int QH>
-__device__ __forceinline__ void store_pair11(unsigned char* buf, int r, int s, float a_re, float b_re, float a_im,
-                                             float b_im, int sc)
+__device__ __forceinline__ void store_pair11(unsigned char* buf, int r, int s, nf2 a, nf2 b)
 {
-    store_pair_g<geom11<D, QH>>(buf, r, s, a_re, b_re, a_im, b_im, sc);
+    store_pair_g<geom11<D, QH>>(buf, r, s, a, b);
 }
 
 // the chunk's float4 (2 input samples) a lane loads as its unit u, instruction f, with
@@ -299,9 +322,10 @@ __device__ __forceinline__ int q13(int u, int f)
 
 // chunk (registers) + its raw halo (hsrc: HP float4 in LDS) -> the split phase planes at scale 2^sc.
 // CLOAD: v[u D + f] is the chunk's float4 q13(u, f) (k_fir_mfma13's whole-line loads), else float4
-// (tid + NT u) D + f (a thread's D float4 adjacent).
-template <int D, int QH, bool CLOAD>
-__device__ __forceinline__ void put_split11(int tid, unsigned char* buf, const float4* hsrc, const float4 (&v)[4], int sc)
+// (tid + NT u) D + f (a thread's D float4 adjacent). Every sample is scaled as loaded (a packed
+// multiply per (re, im) register pair, MUL: scale2), before the lanes exchange and split them.
+template <int D, int QH, bool CLOAD, bool MUL>
+__device__ __forceinline__ void put_split11_as(int tid, unsigned char* buf, const float4* hsrc, const float4 (&v)[4], int sc)
 {
     using G = geom11<D, QH>;
     if (tid < D * (G::H / 2)) { // halo: phase r, pair pi from the raw halo samples
@@ -309,7 +333,7 @@ __device__ __forceinline__ void put_split11(int tid, unsigned char* buf, const f
         const int sr = r == 0 ? 0 : D - r;
         const int pa = D * (2 * pi) + sr, pb = D * (2 * pi + 1) + sr;
         const float2 a = f4_sample(hsrc[pa >> 1], pa & 1), bb = f4_sample(hsrc[pb >> 1], pb & 1);
-        store_pair11<D, QH>(buf, r, 2 * pi, a.x, bb.x, a.y, bb.y, sc);
+        store_pair11<D, QH>(buf, r, 2 * pi, scale2<MUL>(a.x, a.y, sc), scale2<MUL>(bb.x, bb.y, sc));
     }
     if constexpr (CLOAD) {
         // float4 q holds samples 2q, 2q + 1: phase offsets 2q mod D (+1) at time 2q / D, the pair
@@ -323,18 +347,17 @@ __device__ __forceinline__ void put_split11(int tid, unsigned char* buf, const f
             for (int f = 0; f < D; ++f) {
                 const int q = q13<D>(u, f);
                 const bool k = (q & (D / 2)) != 0;
-                const float4 x = v[u * D + f];
-                const float kre = k ? x.z : x.x, kim = k ? x.w : x.y; // offset k: kept
-                const float sre = k ? x.x : x.z, sim = k ? x.y : x.w; // offset 1 - k: the partner's
+                const nf2 x0 = scale2<MUL>(v[u * D + f].x, v[u * D + f].y, sc), x1 = scale2<MUL>(v[u * D + f].z, v[u * D + f].w, sc);
+                const float kre = k ? x1.x : x0.x, kim = k ? x1.y : x0.y; // offset k: kept
+                const float sre = k ? x0.x : x1.x, sim = k ? x0.y : x1.y; // offset 1 - k: the partner's
                 const float rre = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sre), XCHG, 0xf, 0xf, true));
                 const float rim = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sim), XCHG, 0xf, 0xf, true));
                 const int sr = D == 4 ? 2 * (q & 1) + (int)k : (int)k;
                 const int r = sr == 0 ? 0 : D - sr;
                 const int s = G::H + 2 * (q / D);
-                if (k)
-                    store_pair11<D, QH>(buf, r, s, rre, kre, rim, kim, sc);
-                else
-                    store_pair11<D, QH>(buf, r, s, kre, rre, kim, rim, sc);
+                // the pair in time order, by selects: a per-lane branch around the split's inline asm
+                // would stay a branch (both sides executed, lanes masked)
+                store_pair11<D, QH>(buf, r, s, nf2{ k ? rre : kre, k ? rim : kim }, nf2{ k ? kre : rre, k ? kim : rim });
             }
     } else {
 #pragma unroll
@@ -346,10 +369,19 @@ __device__ __forceinline__ void put_split11(int tid, unsigned char* buf, const f
                 const int la = sr, lb = D + sr;
                 const float2 a = f4_sample(v[u * D + la / 2], la & 1);
                 const float2 bb = f4_sample(v[u * D + lb / 2], lb & 1);
-                store_pair11<D, QH>(buf, r, G::H + i0, a.x, bb.x, a.y, bb.y, sc);
+                store_pair11<D, QH>(buf, r, G::H + i0, scale2<MUL>(a.x, a.y, sc), scale2<MUL>(bb.x, bb.y, sc));
             }
         }
     }
+}
+// the form of the scale (workgroup-uniform) chosen once for the chunk
+template <int D, int QH, bool CLOAD>
+__device__ __forceinline__ void put_split11(int tid, unsigned char* buf, const float4* hsrc, const float4 (&v)[4], int sc)
+{
+    if (__builtin_expect(scale_is_mul(sc), 1))
+        put_split11_as<D, QH, CLOAD, true>(tid, buf, hsrc, v, sc);
+    else
+        put_split11_as<D, QH, CLOAD, false>(tid, buf, hsrc, v, sc);
 }
 
 // A lane's place in the decimators' tile: component c and block b of its A row (row_base: byte
