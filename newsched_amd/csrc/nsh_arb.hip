@@ -17,11 +17,10 @@
 //     index      Per output, in 64 bits without a 128-bit product: with step = si 2^32 + sf and
 //                phase = pi 2^32 + pf, lo = pf + n sf (n < 2^31, so below 2^63 + 2^32),
 //                k = pi + n si + (lo >> 32), fraction = lo & 0xffffffff.
-//     stage      The window, each sample read from HBM once per workgroup with 8-byte non-temporal
-//                loads (ring pointers are only 8-byte aligned), 8 pairs per lane in flight as in
-//                k_resamp; the stream's first tiles read through virt() (history, zeros). The taps
-//                go to LDS as interleaved (h, d) pairs, one ds_read_b64 per tap: tap k = j + q F at
-//                entry q P + j + (j >> 5) pad, P = F + pad.
+//     stage      The window by nsh::stage_window (nsh_stream_tile.hpp), with 8-byte non-temporal
+//                loads (ring pointers are only 8-byte aligned). The taps go to LDS as interleaved
+//                (h, d) pairs, one ds_read_b64 per tap: tap k = j + q F at entry
+//                q P + j + (j >> 5) pad, P = F + pad.
 //     FIR        q ascending, w = fmaf(mu, d, h), then one FMA per component: acc = fmaf(w, x, acc).
 //                The order is fixed per output, whatever the tile and the call it falls into. Taps
 //                j + q F >= L (the padding up to Q F) are skipped, never multiplied: only the last q
@@ -32,7 +31,8 @@
 //                broadcast: conflict-free with pad = 0. With F = 64, j and j + 32 would share a bank
 //                pair; the plan moves the upper half of each row by the pad in [0, 31] with the
 //                smallest worst-case multiplicity over 32 consecutive outputs at sampled phases
-//                (two entries on a bank pair can remain: 64 filters, 32 bank pairs).
+//                (two entries on a bank pair can remain: 64 filters, 32 bank pairs). This choice and
+//                the next are nsh_stream_layout.hpp's arb_layout_of.
 //                Samples, r >= 1 (k_arb<R,1>): consecutive outputs read samples that never
 //                decrease and rise by at most one per lane: at most 32 consecutive samples (equal
 //                ones are a broadcast), conflict-free with the image packed, as in k_resamp<8,1>.
@@ -40,14 +40,13 @@
 //                padding: sample s at entry s + (s >> a), the plan picks the a in {31 (none), 6, ..., 1}
 //                with the smallest worst-case multiplicity at sampled phases (ties: the larger a).
 //     store      Through LDS: after a barrier the lanes write their outputs over the sample image at
-//                their place in the tile, and the workgroup reads the tile back linearly: 16-byte
-//                non-temporal stores when out is 16-byte aligned (T is even), the 8-byte path otherwise.
+//                their place in the tile, and nsh::store_tile reads the tile back linearly (T is even).
 //     history    Workgroup 0 writes hist_out: the Q-1 raw samples before in[c], c the inputs the call
 //                consumes. An advancing call (n_out = 0) is this workgroup alone.
 //   Instantiations: <4,1> for r >= 1 (T = 1024); <4,0>, <2,0>, <1,0> for r < 1 by the T the window allows.
 //   Accuracy: fp32 throughout. Non-finite samples propagate by IEEE arithmetic: output n is
 //   non-finite exactly when one of its products holds the sample.
-#include "nsh_common.hpp"
+#include "nsh_stream_tile.hpp"
 
 #include "nsh_arb_span.hpp"
 
@@ -58,13 +57,12 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kStage = 8;        // sample pairs a lane loads before it stores the first
-constexpr int kMaxWindow = 8192; // samples of a tile's window
+constexpr int kBlock = nsh::kStreamBlock;
+constexpr int kStage = 8; // sample pairs a lane loads before it stores the first
+constexpr int kMaxWindow = nsh::kStreamMaxTile;
 
+using nsh::fma2;
 using nsh::ld_nt;
-using nsh::nf2;
-using nsh::nf4;
 using nsh::virt;
 
 struct arb_args {
@@ -96,7 +94,8 @@ __global__ __launch_bounds__(kBlock) void k_arb(const float2* __restrict__ in,
     const int tid = threadIdx.x;
     const int H = p.Q - 1;
 
-    if (blockIdx.x == 0) { // history for the next call: the Q-1 raw samples before in[consumed]
+    // nsh::store_history's loop with two bounds: the history ends at in[consumed], the input at in[n_in]
+    if (blockIdx.x == 0) {
         for (int j = tid; j < H; j += kBlock) hist_out[j] = virt(in, hist_in, p.consumed - H + j, p.n_in, p.Q);
     }
     if (p.n_out <= 0) return; // an advancing call
@@ -116,25 +115,11 @@ __global__ __launch_bounds__(kBlock) void k_arb(const float2* __restrict__ in,
     const int64_t g0 = i0 - H; // stream sample (of this call) at window position 0
     const int count = i1 - i0 + p.Q < p.wmax ? (int)(i1 - i0) + p.Q : p.wmax;
 
-    auto stage = [&](auto load) {
-        for (int s0 = 2 * tid; s0 < count; s0 += 2 * kBlock * kStage) {
-            float2 x0[kStage], x1[kStage];
-#pragma unroll
-            for (int u = 0; u < kStage; ++u) {
-                const int i = s0 + 2 * kBlock * u;
-                x0[u] = i < count ? load(i) : make_float2(0.f, 0.f);
-                x1[u] = i + 1 < count ? load(i + 1) : make_float2(0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < kStage; ++u) {
-                const int i = s0 + 2 * kBlock * u;
-                if (i < count) {
-                    xs[entry(i)] = x0[u];
-                    if (i + 1 < count) xs[entry(i + 1)] = x1[u];
-                }
-            }
-        }
+    const auto put = [&](int i, float2 x0, float2 x1) {
+        xs[entry(i)] = x0;
+        if (i + 1 < count) xs[entry(i + 1)] = x1;
     };
+    const auto stage = [&](auto load) { nsh::stage_window<kBlock, kStage>(count, tid, load, put); };
     if (g0 >= 0 && g0 + count <= p.n_in)
         stage([&](int i) { return ld_nt(in + g0 + i); });
     else
@@ -163,10 +148,8 @@ __global__ __launch_bounds__(kBlock) void k_arb(const float2* __restrict__ in,
 #pragma unroll
         for (int t = 0; t < R; ++t) {
             const float2 hd = hs[t0[t] + q * p.P];
-            const float2 x = xs[entry(s0[t] - q)];
-            const float w = __builtin_fmaf(mu[t], hd.y, hd.x);
-            acc[t].x = __builtin_fmaf(w, x.x, acc[t].x);
-            acc[t].y = __builtin_fmaf(w, x.y, acc[t].y);
+            const float2 x = xs[entry(s0[t] - q)]; // both reads before the first use
+            fma2(acc[t], __builtin_fmaf(mu[t], hd.y, hd.x), x);
         }
     }
     if (qall < p.Q) { // the last, partial row of taps
@@ -174,10 +157,8 @@ __global__ __launch_bounds__(kBlock) void k_arb(const float2* __restrict__ in,
         for (int t = 0; t < R; ++t) {
             if (j[t] + qall * p.F < p.L) {
                 const float2 hd = hs[t0[t] + qall * p.P];
-                const float2 x = xs[entry(s0[t] - qall)];
-                const float w = __builtin_fmaf(mu[t], hd.y, hd.x);
-                acc[t].x = __builtin_fmaf(w, x.x, acc[t].x);
-                acc[t].y = __builtin_fmaf(w, x.y, acc[t].y);
+                const float2 x = xs[entry(s0[t] - qall)]; // both reads before the first use
+                fma2(acc[t], __builtin_fmaf(mu[t], hd.y, hd.x), x);
             }
         }
     }
@@ -187,45 +168,17 @@ __global__ __launch_bounds__(kBlock) void k_arb(const float2* __restrict__ in,
         if (tid + t * kBlock < p.T) xs[tid + t * kBlock] = acc[t];
     __syncthreads();
 
-    if (p.vec) { // T and n0 are even
-        for (int e = 2 * tid; e < p.T; e += 2 * kBlock) {
-            if (n0 + e + 1 < p.n_out) {
-                const nf4 v = *reinterpret_cast<const nf4*>(xs + e);
-                __builtin_nontemporal_store(v, reinterpret_cast<nf4*>(out + n0 + e));
-            } else if (n0 + e < p.n_out) {
-                const nf2 v = *reinterpret_cast<const nf2*>(xs + e);
-                __builtin_nontemporal_store(v, reinterpret_cast<nf2*>(out + n0 + e));
-            }
-        }
-    } else {
-        for (int e = tid; e < p.T; e += kBlock) {
-            if (n0 + e < p.n_out) {
-                const nf2 v = *reinterpret_cast<const nf2*>(xs + e);
-                __builtin_nontemporal_store(v, reinterpret_cast<nf2*>(out + n0 + e));
-            }
-        }
-    }
+    nsh::store_tile<kBlock>(xs, out, n0, p.T, p.n_out, p.vec, tid);
 }
 
-struct arb_plan {
-    int dev = 0;
+struct arb_plan : nsh::stream_plan { // tile: outputs per workgroup T; buf: the (h, d) image
     int L = 0, F = 0, fshift = 0, Q = 0;
     uint64_t step = 0;
-    int R = 0, T = 0, wmax = 0;
-    bool linear = false; // r >= 1: the packed sample image
+    int R = 0, wmax = 0;
     int a = 31, pad = 0, P = 0, hs_at = 0;
-    size_t lds = 0;
-    float2* taps_dev = nullptr;
-    // the instantiation, chosen once at plan creation (pick): the kernel and its launcher
-    const void* fn = nullptr;
+    // the instantiation's launcher (pick)
     void (*launch)(const arb_plan*, const float2*, const float2*, float2*, float2*, const arb_args&, unsigned,
                    hipStream_t) = nullptr;
-    std::string kernel;
-
-    arb_plan() = default;
-    arb_plan(const arb_plan&) = delete;
-    arb_plan& operator=(const arb_plan&) = delete;
-    ~arb_plan() { nsh::dev_free(taps_dev); }
 };
 
 template <int R, bool kLinear>
@@ -233,7 +186,7 @@ void launch_arb(const arb_plan* p, const float2* in, const float2* hin, float2* 
                 unsigned grid, hipStream_t s)
 {
     nsh::launch((k_arb<R, kLinear>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out,
-                (const float2*)p->taps_dev, args);
+                (const float2*)p->buf, args);
 }
 
 template <int R, bool kLinear>
@@ -243,28 +196,6 @@ void pick(arb_plan* p)
     p->fn = (const void*)k_arb<R, kLinear>;
     p->launch = launch_arb<R, kLinear>;
     p->kernel = "k_arb<" + std::to_string(R) + (kLinear ? ",1>" : ",0>");
-}
-
-// Worst number of different entries on one bank pair among 32 consecutive outputs, over sampled
-// phases: output l of the group is at c + l step, value(pos) is the entry it reads.
-template <typename V>
-int worst_multiplicity(uint64_t step, int fshift, V value)
-{
-    int worst = 1;
-    for (int ci = 0; ci < 64; ++ci)
-        for (int cf = 0; cf < 4; ++cf) {
-            // whole inputs and whole filter steps, and quarters of a step on top
-            const uint64_t c = ((uint64_t)ci << (32 + fshift)) + (uint64_t)ci * 0x100000000ull + (uint64_t)cf * 0x40000000ull;
-            int e[32][32], n[32] = {};
-            for (int l = 0; l < 32; ++l) {
-                const int v = value(c + (uint64_t)l * step), b = v & 31;
-                bool seen = false;
-                for (int i = 0; i < n[b]; ++i) seen = seen || e[b][i] == v;
-                if (!seen) e[b][n[b]++] = v;
-            }
-            for (int b = 0; b < 32; ++b) worst = std::max(worst, n[b]);
-        }
-    return worst;
 }
 
 } // namespace
@@ -309,15 +240,16 @@ int nsh_arb_plan_create(int dev, const float* taps_host, int ntaps, int nfilt, d
     p->F = nfilt;
     p->fshift = nsh_arb::filt_shift(nfilt);
     p->Q = (ntaps + nfilt - 1) / nfilt;
+    p->hist = p->Q - 1;
     p->step = nsh_arb::step_of(rate, nfilt);
     const int fshift = p->fshift;
     const uint64_t step = p->step, unit = 1ull << (32 + fshift); // one input sample
-    p->linear = step <= unit;
+    const nsh::arb_layout lay = nsh::arb_layout_of(step, fshift);
     // T outputs span at most floor((T-1) step / unit) + 1 inputs after the first one's
     const auto window = [&](int T) { return (int)(((uint64_t)(T - 1) * step) >> (32 + fshift)) + 1 + p->Q; };
     // the largest T the window allows: (T-1) step < (kMaxWindow - Q) unit, at least 111 (r = 1/64, Q = 1024)
     const uint64_t t_fit = ((uint64_t)(kMaxWindow - p->Q) * unit - 1) / step + 1;
-    if (p->linear)
+    if (lay.linear)
         pick<4, true>(p.get());
     else if (t_fit >= 4 * kBlock)
         pick<4, false>(p.get());
@@ -325,32 +257,13 @@ int nsh_arb_plan_create(int dev, const float* taps_host, int ntaps, int nfilt, d
         pick<2, false>(p.get());
     else
         pick<1, false>(p.get());
-    p->T = (int)std::min<uint64_t>((uint64_t)p->R * kBlock, t_fit) & ~1; // even: 16-byte stores
-    p->wmax = window(p->T);
+    p->tile = (int)std::min<uint64_t>((uint64_t)p->R * kBlock, t_fit) & ~1; // even: 16-byte stores
+    p->wmax = window(p->tile);
     if (p->wmax > kMaxWindow) return nsh::fail_msg("nsh_arb_plan_create: internal: window too long");
-    if (!p->linear) {
-        int best = 1 << 30;
-        for (int a : { 31, 6, 5, 4, 3, 2, 1 }) {
-            const int m = worst_multiplicity(step, fshift, [&](uint64_t pos) {
-                const int s = (int)(pos >> (32 + fshift));
-                return s + (s >> a);
-            });
-            if (m < best) best = m, p->a = a;
-        }
-    }
-    if (nfilt == 64) {
-        int best = 1 << 30;
-        for (int pad = 0; pad < 32; ++pad) {
-            const int m = worst_multiplicity(step, fshift, [&](uint64_t pos) {
-                const int j = (int)((pos >> 32) & 63);
-                return j + (j >> 5) * pad;
-            });
-            if (m < best) best = m, p->pad = pad;
-        }
-    }
+    p->a = lay.a, p->pad = lay.pad;
     p->P = nfilt + p->pad;
     // the sample image (the tile's outputs take its place later), then the taps, 16-byte aligned
-    p->hs_at = (std::max(p->wmax + (p->wmax >> p->a) + 1, p->T) + 1) / 2 * 2;
+    p->hs_at = (std::max(p->wmax + (p->wmax >> p->a) + 1, p->tile) + 1) / 2 * 2;
     p->lds = ((size_t)p->hs_at + (size_t)p->Q * p->P) * sizeof(float2);
     // at most 96 KiB of samples (8192 at a = 1) and 24 KiB of taps (F = 64, pad = 31), within the CU's 160 KiB
     std::vector<float> d((size_t)ntaps);
@@ -360,10 +273,7 @@ int nsh_arb_plan_create(int dev, const float* taps_host, int ntaps, int nfilt, d
         const int j = k & (nfilt - 1), q = k >> fshift;
         host[(size_t)q * p->P + j + (j >> 5) * p->pad] = make_float2(taps_host[k], d[k]);
     }
-    hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-    if (e == hipSuccess) e = hipMalloc(&p->taps_dev, host.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpy(p->taps_dev, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return nsh::fail(e, "nsh_arb_plan_create");
+    if (const int rc = p->upload(host.data(), host.size() * sizeof(float2), "nsh_arb_plan_create")) return rc;
     *plan = p.release();
     return 0;
 }
@@ -374,9 +284,9 @@ int nsh_arb_plan_destroy(void* plan)
     return 0;
 }
 
-int nsh_arb_tile(void* plan) { return plan ? static_cast<arb_plan*>(plan)->T : 0; }
+int nsh_arb_tile(void* plan) { return plan ? static_cast<arb_plan*>(plan)->tile : 0; }
 const char* nsh_arb_kernel(void* plan) { return plan ? static_cast<arb_plan*>(plan)->kernel.c_str() : ""; }
-int nsh_arb_history(void* plan) { return plan ? static_cast<arb_plan*>(plan)->Q - 1 : 0; }
+int nsh_arb_history(void* plan) { return plan ? static_cast<arb_plan*>(plan)->hist : 0; }
 int nsh_arb_plan_step(void* plan, uint64_t* step)
 {
     if (!plan || !step) return nsh::fail_msg("nsh_arb_plan_step: null pointer");
@@ -389,7 +299,7 @@ int nsh_arb_resamp_ccf(void* plan, const float* in, int64_t n_in, const float* h
 {
     nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
     auto* p = static_cast<arb_plan*>(plan);
-    // what needs no plan comes first, as in check_stream_call
+    // what needs no plan comes first, as in nsh::check_stream_call
     if (hist_in && hist_in == hist_out) return nsh::fail_msg("nsh_arb_resamp_ccf: hist_out must not alias hist_in");
     if (n_in > 0 && (!in || (n_out > 0 && !out))) return nsh::fail_msg("nsh_arb_resamp_ccf: null input or output");
     if (n_in > nsh_arb::kMaxItems || n_out > nsh_arb::kMaxItems)
@@ -409,9 +319,9 @@ int nsh_arb_resamp_ccf(void* plan, const float* in, int64_t n_in, const float* h
     a.n_out = n_out;
     a.consumed = s.n_consumed;
     a.L = p->L, a.F = p->F, a.fshift = p->fshift, a.Q = p->Q;
-    a.T = p->T, a.wmax = p->wmax, a.a = p->a, a.pad = p->pad, a.P = p->P, a.hs_at = p->hs_at;
-    a.vec = (uintptr_t)out % 16 == 0 && p->T % 2 == 0 ? 1 : 0;
-    const int64_t grid = std::max<int64_t>((n_out + p->T - 1) / p->T, 1);
+    a.T = p->tile, a.wmax = p->wmax, a.a = p->a, a.pad = p->pad, a.P = p->P, a.hs_at = p->hs_at;
+    a.vec = nsh::store_vec16(out, p->tile);
+    const int64_t grid = std::max<int64_t>((n_out + p->tile - 1) / p->tile, 1);
     p->launch(p, (const float2*)in, (const float2*)hist_in, (float2*)hist_out, (float2*)out, a, (unsigned)grid,
               nsh::S(stream));
     NSH_CK_LAUNCH("nsh_arb_resamp_ccf");

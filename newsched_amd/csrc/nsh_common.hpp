@@ -214,27 +214,6 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// Argument checks of the one-kernel stream entry points (nsh_fir_xlat_ccf, nsh_pfb_channelizer_ccf),
-// in their documented order; what needs no plan comes first, so that every refusal can be checked
-// without a device. The plan has L taps and makes T outputs per workgroup. Returns the refusal's
-// code, or 0 with *grid = the workgroups to launch (0: nothing to do).
-template <typename Plan>
-inline int check_stream_call(const char* name, const Plan* p, const float* in, const float* hist_in, const float* hist_out,
-                             const float* out, int64_t n_out, int64_t n_out_max, unsigned* grid)
-{
-    const auto refuse = [name](const char* what) { return fail_msg((std::string(name) + what).c_str()); };
-    *grid = 0;
-    if (hist_in && hist_in == hist_out) return refuse(": hist_out must not alias hist_in");
-    if (n_out > 0 && (!in || !out)) return refuse(": null input or output");
-    if (!p) return refuse(": null plan");
-    if (n_out <= 0) return 0;
-    if (!hist_out && p->L > 1) return refuse(": hist_out is required (ntaps-1 samples)");
-    const int64_t g = (n_out + p->T - 1) / p->T;
-    if (g > 0x7fffffff || n_out > n_out_max) return refuse(": too many outputs for one call");
-    *grid = (unsigned)g;
-    return 0;
-}
-
 } // namespace nsh
 
 #define NSH_CK(expr)                                                    \

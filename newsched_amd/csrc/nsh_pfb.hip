@@ -15,9 +15,8 @@
 //              step m0 - (Q-1) + j in stream order, x[(m0-Q+1+j) M - (M-1) + c] in column c, so
 //              branch p reads column M-1-p. (T+Q-1) M samples, each read from HBM once per
 //              workgroup with 8-byte non-temporal loads (ring pointers are only 8-byte aligned),
-//              8 pairs per lane in flight as in k_fir_xlat. The stream's first and last tiles read
-//              through virt() (history, zeros). The taps go to LDS as hs[q][p], zero-padded to a
-//              multiple of 4 rows.
+//              in the order of nsh::stage_window (nsh_stream_tile.hpp), in a loop of the kernel's own.
+//              The taps go to LDS as hs[q][p], zero-padded to a multiple of 4 rows.
 //     FIR      Lane (tg, p) = (tid / M, tid mod M) keeps the R consecutive time steps tg R + t of
 //              branch p. It walks the taps in chunks of 4 and
 //              holds the R + 3 rows the chunk needs in registers; the next chunk moves R - 1 of
@@ -50,7 +49,7 @@
 //   Accuracy: fp32 throughout. The DFT mixes the branches, so errors are relative to the largest
 //   channel of a time step, not to each channel. Non-finite samples propagate by IEEE arithmetic: a
 //   NaN in the L-tap window of a time step makes all M channels of that step NaN and no other.
-#include "nsh_common.hpp"
+#include "nsh_stream_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -60,12 +59,13 @@
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = nsh::kStreamBlock;
 constexpr int kR = 8;      // consecutive time steps a lane keeps
 constexpr int kQC = 4;     // taps per chunk
 constexpr int kRounds = 2; // store rounds: kR / kRounds time steps each
 constexpr int kStage = 8;  // sample pairs a lane loads before it stores the first
 
+using nsh::fma2;
 using nsh::ilog2;
 using nsh::ld_nt;
 using nsh::nf2;
@@ -117,6 +117,9 @@ __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
     const int64_t g0 = (m0 - (Q - 1)) * M - (M - 1); // stream sample (of this call) at window position 0
     const int count = rows * M;
 
+    // nsh::stage_window's loop, kept apart: the window is whole rows, so count is even and one test
+    // serves both loads of a pair. Through the shared loop the compiler made other memory
+    // instructions (a 16-byte load split in two, 40 to 110 instructions more per instantiation).
     auto stage = [&](auto load) {
         for (int i0 = 2 * tid; i0 < count; i0 += 2 * kBlock * kStage) {
             float2 x0[kStage], x1[kStage];
@@ -142,9 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
     else
         stage([&](int i) { return virt(in, hist_in, g0 + i, n_in, L); });
     for (int i = tid; i < Qp * M; i += kBlock) hs[i] = hp[i];
-    if (blockIdx.x == 0) { // history for the next call: the L-1 raw samples before in[n_in]
-        for (int j = tid; j < L - 1; j += kBlock) hist_out[j] = virt(in, hist_in, n_in - (L - 1) + j, n_in, L);
-    }
+    if (blockIdx.x == 0) nsh::store_history<kBlock>(in, hist_in, hist_out, n_in, L, tid);
 
     float2 w[LOG2M > 1 ? LOG2M - 1 : 1];
 #pragma unroll
@@ -175,19 +176,13 @@ __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
 #pragma unroll
             for (int dq = 0; dq < kQC; ++dq)
 #pragma unroll
-                for (int t = 0; t < kR; ++t) {
-                    acc[t].x = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].x, acc[t].x);
-                    acc[t].y = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].y, acc[t].y);
-                }
+                for (int t = 0; t < kR; ++t) fma2(acc[t], h[dq], xw[t + kQC - 1 - dq]);
         } else { // the chunk holds taps at or past L: tap by tap, none outside
 #pragma unroll
             for (int dq = 0; dq < kQC; ++dq) {
                 if (q0 + dq < qv) {
 #pragma unroll
-                    for (int t = 0; t < kR; ++t) {
-                        acc[t].x = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].x, acc[t].x);
-                        acc[t].y = __builtin_fmaf(h[dq], xw[t + kQC - 1 - dq].y, acc[t].y);
-                    }
+                    for (int t = 0; t < kR; ++t) fma2(acc[t], h[dq], xw[t + kQC - 1 - dq]);
                 }
             }
         }
@@ -259,37 +254,26 @@ __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
     }
 }
 
-struct pfb_plan {
-    int dev = 0;
-    int L = 0, M = 0, Q = 0, Qp = 0, T = 0;
-    size_t lds = 0;
-    float* hp_dev = nullptr;  // Qp M taps, then the twiddles
-    float2* tw_dev = nullptr; // inside hp_dev's allocation
-    // the instantiation, chosen once at plan creation (setup): the kernel and its launcher
-    const void* fn = nullptr;
+struct pfb_plan : nsh::stream_plan { // tile: time steps per workgroup T; buf: Qp M taps, then the twiddles
+    int L = 0, M = 0, Q = 0, Qp = 0;
+    // the instantiation's launcher (setup)
     void (*launch)(const pfb_plan*, const float2*, const float2*, float2*, float2*, int64_t, int, unsigned,
                    hipStream_t) = nullptr;
-    std::string kernel;
-
-    pfb_plan() = default;
-    pfb_plan(const pfb_plan&) = delete;
-    pfb_plan& operator=(const pfb_plan&) = delete;
-    ~pfb_plan() { nsh::dev_free(hp_dev); }
 };
 
 template <int M>
 void launch_pfb(const pfb_plan* p, const float2* in, const float2* hin, float2* hout, float2* out, int64_t n_out, int vec,
                 unsigned grid, hipStream_t s)
 {
-    nsh::launch((k_pfb<M>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out, (const float*)p->hp_dev,
-                (const float2*)p->tw_dev, p->L, p->Q, p->Qp, n_out, vec);
+    nsh::launch((k_pfb<M>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out, (const float*)p->buf,
+                (const float2*)((const float*)p->buf + p->Qp * M), p->L, p->Q, p->Qp, n_out, vec);
 }
 
 template <int M>
 void setup(pfb_plan* p)
 {
     using g = geom<M>;
-    p->T = g::T;
+    p->tile = g::T;
     p->fn = (const void*)k_pfb<M>;
     p->launch = launch_pfb<M>;
     p->lds = (size_t)g::row_entry(g::T + p->Q - 1) * sizeof(float2) + (size_t)p->Qp * M * sizeof(float) +
@@ -312,6 +296,7 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
     auto p = std::make_unique<pfb_plan>();
     p->dev = dev;
     p->L = ntaps;
+    p->hist = ntaps - 1;
     p->M = nchans;
     p->Q = Q;
     p->Qp = (Q + kQC - 1) / kQC * kQC;
@@ -344,11 +329,8 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
         }
     }
     // at most 37.75 KiB (38 656 bytes, M = 32 with 1024 taps; M = 64 with 1024 taps: 38 400)
-    hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
-    if (e == hipSuccess) e = hipMalloc(&p->hp_dev, host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->hp_dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return nsh::fail(e, "nsh_pfb_plan_create");
-    p->tw_dev = reinterpret_cast<float2*>(p->hp_dev + ntap); // ntap is a multiple of 8 floats
+    // the twiddles start ntap floats in, a multiple of 8 floats
+    if (const int rc = p->upload(host.data(), host.size() * sizeof(float), "nsh_pfb_plan_create")) return rc;
     *plan = p.release();
     return 0;
 }
@@ -359,7 +341,7 @@ int nsh_pfb_plan_destroy(void* plan)
     return 0;
 }
 
-int nsh_pfb_tile(void* plan) { return plan ? static_cast<pfb_plan*>(plan)->T : 0; }
+int nsh_pfb_tile(void* plan) { return plan ? static_cast<pfb_plan*>(plan)->tile : 0; }
 const char* nsh_pfb_kernel(void* plan) { return plan ? static_cast<pfb_plan*>(plan)->kernel.c_str() : ""; }
 
 int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n_out,
@@ -368,10 +350,10 @@ int nsh_pfb_channelizer_ccf(void* plan, const float* in, const float* hist_in, f
     nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
     auto* p = static_cast<pfb_plan*>(plan);
     unsigned grid = 0;
-    const int rc =
-        nsh::check_stream_call("nsh_pfb_channelizer_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 128, &grid);
+    const int rc = nsh::check_stream_call("nsh_pfb_channelizer_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 128,
+                                          "ntaps-1", "outputs", &grid);
     if (rc || !grid) return rc;
-    const int vec = (uintptr_t)out % 16 == 0 ? 1 : 0;
+    const int vec = nsh::store_vec16(out, p->tile * p->M);
     p->launch(p, (const float2*)in, (const float2*)hist_in, (float2*)hist_out, (float2*)out, n_out, vec, grid,
               nsh::S(stream));
     NSH_CK_LAUNCH("nsh_pfb_channelizer_ccf");

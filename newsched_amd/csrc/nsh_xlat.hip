@@ -33,7 +33,7 @@
 //                   Instantiations by decimation, T D <= 8192 samples (two workgroups per CU on
 //                   160 KiB when 2^a >= 8): D <= 4 <8,1>, <= 8 <4,1>, <= 16 <4,2>, <= 32 <4,4>,
 //                   <= 64 <2,4>.
-#include "nsh_common.hpp"
+#include "nsh_stream_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -43,10 +43,11 @@
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = nsh::kStreamBlock;
 constexpr int kUnroll = 4;
 constexpr int kStage = 8; // sample pairs a lane loads before it rotates the first (k_fir_xlat's staging)
 
+using nsh::fma2;
 using nsh::nf4;
 using nsh::virt;
 
@@ -135,11 +136,11 @@ __global__ __launch_bounds__(kBlock) void k_fir_xlat(const float2* __restrict__ 
     const int64_t g0 = m0 * D - (L - 1);           // stream sample (of this call) at window position 0
     const int count = (T - 1) * D + L;
 
-    // stage and rotate: a lane takes two neighbouring samples, one sincospif and the step phasor.
-    // kStage pairs per lane per pass, every load of a pass issued before the first is used (a pass
-    // of one pair per lane waits out the HBM latency 16 times per 8192-sample window).
-    // A workgroup whose window lies inside the input loads it directly, the stream's first and
-    // last ones through virt().
+    // stage and rotate: nsh::stage_window's loop (nsh_stream_tile.hpp) with the rotation in place of
+    // its put: a lane's two neighbouring samples take one sincospif and the step phasor. Kept apart,
+    // like the history loop below: through the shared pieces the prologue and the first and last
+    // windows' code came out in another order, and D = 64 measured 1 to 2 % slower
+    // (profiles/stream_refactor_ab.log). The direct loads are plain ones, not ld_nt.
     auto stage = [&](auto load) {
         for (int i0 = 2 * tid; i0 < count; i0 += 2 * kBlock * kStage) {
             float2 x0[kStage], x1[kStage];
@@ -194,19 +195,12 @@ __global__ __launch_bounds__(kBlock) void k_fir_xlat(const float2* __restrict__ 
 #pragma unroll
                     for (int i = 0; i < 8; ++i) g[i] = grev[q0 + i];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        acc[r].x = __builtin_fmaf(g[i], x[i].x, acc[r].x);
-                        acc[r].y = __builtin_fmaf(g[i], x[i].y, acc[r].y);
-                    }
+                    for (int i = 0; i < 8; ++i) fma2(acc[r], g[i], x[i]);
                 } else if (q0 + 8 > qlo && q0 < qhi) { // the part's edges: tap by tap, none outside
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const int q = q0 + i;
-                        if (q >= qlo && q < qhi) {
-                            const float g = grev[q];
-                            acc[r].x = __builtin_fmaf(g, x[i].x, acc[r].x);
-                            acc[r].y = __builtin_fmaf(g, x[i].y, acc[r].y);
-                        }
+                        if (q >= qlo && q < qhi) fma2(acc[r], grev[q], x[i]);
                     }
                 }
             }
@@ -239,25 +233,15 @@ __global__ __launch_bounds__(kBlock) void k_fir_xlat(const float2* __restrict__ 
     }
 }
 
-struct xlat_plan {
-    int dev = 0;
+struct xlat_plan : nsh::stream_plan { // tile: outputs per workgroup T; buf: the reversed taps
     int L = 0, D = 0;
-    int R = 0, S = 0, T = 0;
+    int R = 0, S = 0;
     int a = 0, Lc = 0;
-    size_t lds = 0;
     uint64_t inc = 0;
     float2 step = { 1.f, 0.f };
-    float* grev_dev = nullptr;
-    // the instantiation, chosen once at plan creation (pick): the kernel and its launcher
-    const void* fn = nullptr;
+    // the instantiation's launcher (pick)
     void (*launch)(const xlat_plan*, const float2*, const float2*, float2*, float2*, int64_t, uint64_t, unsigned,
                    hipStream_t) = nullptr;
-    std::string kernel;
-
-    xlat_plan() = default;
-    xlat_plan(const xlat_plan&) = delete;
-    xlat_plan& operator=(const xlat_plan&) = delete;
-    ~xlat_plan() { nsh::dev_free(grev_dev); }
 };
 
 int phase_inc(double t, uint64_t* inc)
@@ -281,7 +265,7 @@ void launch_xlat(const xlat_plan* p, const float2* in, const float2* hin, float2
                  uint64_t first, unsigned grid, hipStream_t s)
 {
     nsh::launch((k_fir_xlat<R, S>), dim3(grid), dim3(kBlock), (uint32_t)p->lds, s, in, hin, hout, out,
-                (const float*)p->grev_dev, p->L, p->D, p->a, p->Lc, n_out, p->inc, first, p->step);
+                (const float*)p->buf, p->L, p->D, p->a, p->Lc, n_out, p->inc, first, p->step);
 }
 
 template <int R, int S>
@@ -330,6 +314,7 @@ int nsh_fir_xlat_plan_create(int dev, const float* taps_host, int ntaps, int dec
     auto p = std::make_unique<xlat_plan>();
     p->dev = dev;
     p->L = ntaps;
+    p->hist = ntaps - 1;
     p->D = decim;
     p->inc = inc;
     p->step = step_phasor(inc);
@@ -343,21 +328,18 @@ int nsh_fir_xlat_plan_create(int dev, const float* taps_host, int ntaps, int dec
         pick<4, 4>(p.get());
     else
         pick<2, 4>(p.get());
-    p->T = kBlock * p->R / p->S;
+    p->tile = kBlock * p->R / p->S;
     p->kernel = "k_fir_xlat<" + std::to_string(p->R) + "," + std::to_string(p->S) + ">";
     const int RD = p->R * decim;
     while (RD % (2 << p->a) == 0) ++p->a; // 2^a: the largest power of two in R D (R is even: a >= 1)
     p->Lc = ((ntaps + p->S - 1) / p->S + 7) / 8 * 8;
     // the window, the 8-sample blocks' overrun past the last lane's span, then the padding
-    const int wn = p->T * decim + ntaps + 8;
+    const int wn = p->tile * decim + ntaps + 8;
     p->lds = (size_t)(wn + (wn >> p->a) + 1) * sizeof(float2);
     // at most 110 KiB (D = 63, L = 1024: a = 1), within the CU's 160 KiB
-    hipError_t e = hipFuncSetAttribute(p->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds);
     std::vector<float> grev((size_t)ntaps + 8, 0.f);
     for (int q = 0; q < ntaps; ++q) grev[q] = taps_host[ntaps - 1 - q];
-    if (e == hipSuccess) e = hipMalloc(&p->grev_dev, grev.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->grev_dev, grev.data(), grev.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return nsh::fail(e, "nsh_fir_xlat_plan_create");
+    if (const int rc = p->upload(grev.data(), grev.size() * sizeof(float), "nsh_fir_xlat_plan_create")) return rc;
     *plan = p.release();
     return 0;
 }
@@ -375,7 +357,7 @@ int nsh_fir_xlat_phase_inc(void* plan, uint64_t* inc)
     return 0;
 }
 
-int nsh_fir_xlat_tile(void* plan) { return plan ? static_cast<xlat_plan*>(plan)->T : 0; }
+int nsh_fir_xlat_tile(void* plan) { return plan ? static_cast<xlat_plan*>(plan)->tile : 0; }
 const char* nsh_fir_xlat_kernel(void* plan) { return plan ? static_cast<xlat_plan*>(plan)->kernel.c_str() : ""; }
 
 int nsh_fir_xlat_ccf(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n_out,
@@ -384,7 +366,8 @@ int nsh_fir_xlat_ccf(void* plan, const float* in, const float* hist_in, float* h
     nsh::launch_events_guard timing_guard; // the armed event pair never outlives this call
     auto* p = static_cast<xlat_plan*>(plan);
     unsigned grid = 0;
-    const int rc = nsh::check_stream_call("nsh_fir_xlat_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 64, &grid);
+    const int rc = nsh::check_stream_call("nsh_fir_xlat_ccf", p, in, hist_in, hist_out, out, n_out, INT64_MAX / 64, "ntaps-1",
+                                          "outputs", &grid);
     if (rc || !grid) return rc;
     p->launch(p, (const float2*)in, (const float2*)hist_in, (float2*)hist_out, (float2*)out, n_out, first_index, grid,
               nsh::S(stream));

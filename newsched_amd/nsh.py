@@ -145,6 +145,11 @@ def ptr(t) -> int:
     return t if isinstance(t, int) else t.data_ptr()
 
 
+def _opt_ptr(t):
+    """ptr(t), or None (a NULL pointer) for None."""
+    return None if t is None else ptr(t)
+
+
 def stream_ptr(stream=None) -> int:
     import torch
 
@@ -308,8 +313,7 @@ class FirXlatPlan(_Plan):
 
     def __call__(self, x, hist_in, hist_out, y, n_out: int, first_index: int = 0, stream=None):
         """n_out outputs from n_out * decim inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw samples."""
-        check(lib().nsh_fir_xlat_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
-                                     ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
+        check(lib().nsh_fir_xlat_ccf(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n_out,
                                      first_index & (2**64 - 1), stream_ptr(stream)), "nsh_fir_xlat_ccf")
 
 
@@ -332,9 +336,8 @@ class PfbPlan(_Plan):
     def __call__(self, x, hist_in, hist_out, y, n_out: int, stream=None):
         """n_out items of nchans channels from n_out * nchans inputs; hist_in (or None = zeros) /
         hist_out: ntaps-1 raw samples."""
-        check(lib().nsh_pfb_channelizer_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
-                                            ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
-                                            stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
+        check(lib().nsh_pfb_channelizer_ccf(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y),
+                                            n_out, stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
 
 
 class ResampPlan(_Plan):
@@ -358,8 +361,7 @@ class ResampPlan(_Plan):
     def __call__(self, x, hist_in, hist_out, y, n_units: int, stream=None):
         """n_units * interp outputs from n_units * decim inputs; hist_in (or None = zeros) / hist_out:
         `history` = ceil(ntaps / interp) - 1 raw samples."""
-        check(lib().nsh_resamp_ccf(self._h, ptr(x), ptr(hist_in) if hist_in is not None else None,
-                                   ptr(hist_out) if hist_out is not None else None, ptr(y), n_units,
+        check(lib().nsh_resamp_ccf(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n_units,
                                    stream_ptr(stream)), "nsh_resamp_ccf")
 
 
@@ -408,10 +410,8 @@ class ArbPlan(_Plan):
     def __call__(self, x, n_in: int, hist_in, hist_out, y, n_out: int, phase: int = 0, stream=None):
         """n_out outputs (at most span(phase, n_in, ...)) from n_in inputs; hist_in (or None = zeros) /
         hist_out: `history` = ceil(ntaps / nfilt) - 1 raw samples. n_out = 0 only advances."""
-        check(lib().nsh_arb_resamp_ccf(self._h, ptr(x), n_in, ptr(hist_in) if hist_in is not None else None,
-                                       ptr(hist_out) if hist_out is not None else None,
-                                       ptr(y) if y is not None else None, n_out, phase,
-                                       stream_ptr(stream)), "nsh_arb_resamp_ccf")
+        check(lib().nsh_arb_resamp_ccf(self._h, ptr(x), n_in, _opt_ptr(hist_in), _opt_ptr(hist_out),
+                                       _opt_ptr(y), n_out, phase, stream_ptr(stream)), "nsh_arb_resamp_ccf")
 
 
 class FirCascadePlan(_Plan):
@@ -434,7 +434,5 @@ class FirCascadePlan(_Plan):
 
     def __call__(self, x, hist_in, hist_out, y, n_out: int, stream=None):
         """n_out outputs from n_out * decim inputs; hist_in/hist_out: hist_len samples (or 0/None)."""
-        check(lib().nsh_fir_cascade_ccf(self._h, ptr(x) if x is not None else None,
-                                        ptr(hist_in) if hist_in is not None else None,
-                                        ptr(hist_out) if hist_out is not None else None, ptr(y), n_out,
-                                        stream_ptr(stream)), "nsh_fir_cascade_ccf")
+        check(lib().nsh_fir_cascade_ccf(self._h, _opt_ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y),
+                                        n_out, stream_ptr(stream)), "nsh_fir_cascade_ccf")
