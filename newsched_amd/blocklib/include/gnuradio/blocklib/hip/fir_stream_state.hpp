@@ -1,6 +1,6 @@
 // State shared by the gr::hip blocks whose kernels carry an input history from one work() call to
 // the next (fir_filter_ccf, fir_filter_cascade_ccf, freq_xlating_fir_filter_ccf,
-// pfb_channelizer_ccf), because the block API has no history (reference
+// pfb_channelizer_ccf, pfb_synthesizer_ccf, the resamplers), because the block API has no history (reference
 // runtime/include/gnuradio/sync_block.hpp:36-86):
 //   history_state  the libnsh_hip plan and the two history buffers a block ping-pongs between calls
 //   event_pool     the (start, stop) HIP event pairs of a block's timed launches

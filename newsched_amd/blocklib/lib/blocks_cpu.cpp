@@ -4,6 +4,7 @@
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
+#include <gnuradio/blocklib/blocks/pfb_synthesizer_ccf.hpp>
 #include <gnuradio/blocklib/blocks/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
 #include <gnuradio/blocklib/blocks/rotator_cc.hpp>
@@ -356,6 +357,70 @@ work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, 
     std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
     _ext.resize((size_t)(L - 1));
     out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- pfb_synthesizer_ccf: polyphase form, fp32 ------------------------------------------------------
+pfb_synthesizer_ccf::pfb_synthesizer_ccf(int nchans, const std::vector<float>& taps)
+    : resamp_block("pfb_synthesizer_ccf", (unsigned)(nchans > 0 ? nchans : 1), 1), _taps(taps), _nchans(nchans)
+{
+    if (taps.empty()) throw std::invalid_argument("pfb_synthesizer_ccf: no taps");
+    if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
+        throw std::invalid_argument("pfb_synthesizer_ccf: nchans must be a power of two in [2, 64]");
+    _w.resize((size_t)nchans);
+    for (int i = 0; i < nchans; ++i) {
+        const double th = 2.0 * M_PI * (double)i / (double)nchans;
+        _w[i] = gr_complex((float)std::cos(th), (float)std::sin(th));
+    }
+    // the quadrant points exactly
+    _w[0] = gr_complex(1, 0);
+    _w[nchans / 2] = gr_complex(-1, 0);
+    if (nchans >= 4) _w[nchans / 4] = gr_complex(0, 1), _w[3 * nchans / 4] = gr_complex(0, -1);
+}
+
+bool pfb_synthesizer_ccf::start()
+{
+    const size_t M = (size_t)_nchans, Q = (_taps.size() + M - 1) / M;
+    _ext.assign((Q - 1) * M, gr_complex(0, 0)); // zero history at stream start
+    return block::start();
+}
+
+work_return_code_t pfb_synthesizer_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int M = _nchans, L = (int)_taps.size(), Q = (L + M - 1) / M;
+    const int n_in = out[0].n_items / M; // resamp_block::do_work: n items in, n M samples out
+    const size_t H = (size_t)(Q - 1) * M, n_samp = (size_t)n_in * M;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    _ext.resize(H + n_samp);
+    std::memcpy(_ext.data() + H, x, n_samp * sizeof(gr_complex));
+    // v_r[m] = sum_c X[m][c] exp(j 2 pi c r / M), for the history's items too
+    _v.resize(_ext.size());
+    for (size_t j = 0; j < (size_t)(Q - 1 + n_in); ++j) {
+        const gr_complex* X = _ext.data() + j * M;
+        for (int r = 0; r < M; ++r) {
+            float re = 0.f, im = 0.f;
+            for (int c = 0; c < M; ++c) {
+                const gr_complex e = _w[(size_t)((c * r) & (M - 1))];
+                re += X[c].real() * e.real() - X[c].imag() * e.imag();
+                im += X[c].real() * e.imag() + X[c].imag() * e.real();
+            }
+            _v[j * M + r] = gr_complex(re, im);
+        }
+    }
+    for (int m = 0; m < n_in; ++m)
+        for (int r = 0; r < M; ++r) {
+            const gr_complex* v = _v.data() + ((size_t)(m + Q - 1)) * M + r; // v_r[m]
+            float re = 0.f, im = 0.f;
+            for (int k = r, q = 0; k < L; k += M, ++q) { // the taps that meet an item, none beyond L
+                re += _taps[k] * v[-(ptrdiff_t)q * M].real();
+                im += _taps[k] * v[-(ptrdiff_t)q * M].imag();
+            }
+            y[(size_t)m * M + r] = gr_complex(re, im);
+        }
+    std::memmove(_ext.data(), _ext.data() + n_samp, H * sizeof(gr_complex)); // the last Q-1 raw items
+    _ext.resize(H);
+    out[0].n_produced = n_in * M;
     return work_return_code_t::WORK_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
 #include <gnuradio/blocklib/hip/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/pfb_channelizer_ccf.hpp>
+#include <gnuradio/blocklib/hip/pfb_synthesizer_ccf.hpp>
 #include <gnuradio/blocklib/hip/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/rotator_cc.hpp>
 #include <gnuradio/blocklib/hip/synth_source.hpp>
@@ -456,6 +457,49 @@ work_return_code_t pfb_channelizer_ccf::work(std::vector<block_work_input>& in, 
     _state.flip();
     ++_launches;
     out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- polyphase synthesis filterbank ----------------------------------------------------
+pfb_synthesizer_ccf::pfb_synthesizer_ccf(int nchans, const std::vector<float>& taps)
+    : resamp_block("pfb_synthesizer_ccf (hip)", (unsigned)(nchans > 0 ? nchans : 1), 1),
+      _taps(taps),
+      _nchans(nchans),
+      _state("hip::pfb_synthesizer_ccf", nsh_pfb_synth_plan_destroy)
+{
+    if (taps.empty() || taps.size() > 1024) throw std::invalid_argument("hip::pfb_synthesizer_ccf: 1 to 1024 taps");
+    if (nchans < 2 || nchans > 64 || (nchans & (nchans - 1)))
+        throw std::invalid_argument("hip::pfb_synthesizer_ccf: nchans must be a power of two in [2, 64]");
+    if ((taps.size() + (size_t)nchans - 1) / (size_t)nchans > 32)
+        throw std::invalid_argument("hip::pfb_synthesizer_ccf: at most 32 taps per branch");
+}
+
+pfb_synthesizer_ccf::~pfb_synthesizer_ccf() = default;
+
+std::string pfb_synthesizer_ccf::kernel() const
+{
+    return _state.plan() ? nsh_pfb_synth_kernel(_state.plan()) : std::string();
+}
+
+bool pfb_synthesizer_ccf::start()
+{
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_pfb_synth_plan_create(d, _taps.data(), (int)_taps.size(), _nchans, plan), "hip::pfb_synthesizer_ccf plan");
+        return ((_taps.size() + (size_t)_nchans - 1) / (size_t)_nchans - 1) * (size_t)_nchans; // Q-1 items
+    });
+    _state.begin_run(current_stream());
+    return block::start();
+}
+
+work_return_code_t pfb_synthesizer_ccf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_in = out[0].n_items / _nchans; // resamp_block::do_work: n items in, n M samples out
+    check(nsh_pfb_synthesizer_ccf(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                                  (float*)out[0].buffer->write_ptr(), n_in, current_stream()),
+          "hip::pfb_synthesizer_ccf");
+    _state.flip();
+    ++_launches;
+    out[0].n_produced = n_in * _nchans;
     return work_return_code_t::WORK_OK;
 }
 

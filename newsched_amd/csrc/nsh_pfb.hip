@@ -49,7 +49,7 @@
 //   Accuracy: fp32 throughout. The DFT mixes the branches, so errors are relative to the largest
 //   channel of a time step, not to each channel. Non-finite samples propagate by IEEE arithmetic: a
 //   NaN in the L-tap window of a time step makes all M channels of that step NaN and no other.
-#include "nsh_stream_tile.hpp"
+#include "nsh_pfb_geom.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -59,11 +59,7 @@
 
 namespace {
 
-constexpr int kBlock = nsh::kStreamBlock;
-constexpr int kR = 8;      // consecutive time steps a lane keeps
-constexpr int kQC = 4;     // taps per chunk
-constexpr int kRounds = 2; // store rounds: kR / kRounds time steps each
-constexpr int kStage = 8;  // sample pairs a lane loads before it stores the first
+constexpr int kStage = 8; // sample pairs a lane loads before it stores the first
 
 using nsh::fma2;
 using nsh::ilog2;
@@ -72,20 +68,11 @@ using nsh::nf2;
 using nsh::nf4;
 using nsh::virt;
 using nsh::wave_lds_sync;
-
-template <int M>
-struct geom {
-    static constexpr int LOG2M = ilog2(M);
-    static constexpr int G = kBlock / M;    // time groups
-    static constexpr int T = G * kR;        // time steps per workgroup
-    static constexpr int RH = kR / kRounds; // time steps per store round
-    static constexpr int YW = 64 * RH + 64; // entries of a wave's store image
-    __host__ __device__ static constexpr int row_entry(int j) { return (M < 32 ? j + (j >> 3) : j) * M; }
-    __host__ __device__ static constexpr int ypos(int e)
-    {
-        return M >= 32 ? e + (e >> 4) : e + ((e >> (ilog2(RH) + LOG2M)) << LOG2M);
-    }
-};
+using nsh::pfb::geom; // the tile and the LDS images (nsh_pfb_geom.hpp), shared with k_pfb_synth
+using nsh::pfb::kBlock;
+using nsh::pfb::kQC;
+using nsh::pfb::kR;
+using nsh::pfb::kRounds;
 
 template <int M>
 __global__ __launch_bounds__(kBlock) void k_pfb(const float2* __restrict__ in,
@@ -309,25 +296,11 @@ int nsh_pfb_plan_create(int dev, const float* taps_host, int ntaps, int nchans, 
     default: setup<64>(p.get()); break;
     }
     p->kernel = "k_pfb<" + std::to_string(nchans) + ">";
-    const int M = nchans, stages = ilog2(M);
+    const int M = nchans;
     const size_t ntap = (size_t)p->Qp * M;
-    std::vector<float> host(ntap + 2 * (size_t)std::max(stages - 1, 1) * M, 0.f);
+    std::vector<float> host(ntap + nsh::pfb::twiddle_floats(M), 0.f);
     for (int k = 0; k < ntaps; ++k) host[k] = taps_host[k]; // hp[q M + p] = h[p + q M]
-    for (int s = 0; s < stages - 1; ++s) {
-        const int half = M >> (s + 1);
-        for (int q = 0; q < M; ++q) {
-            double c = 1.0, sn = 0.0;
-            if (q & half) {
-                const int i = q & (half - 1);
-                // the quadrant points exactly, the rest from double
-                const double th = 2.0 * M_PI * (double)i / (double)(2 * half);
-                c = std::cos(th), sn = std::sin(th);
-                if (4 * i == 2 * half) c = 0.0, sn = 1.0;
-            }
-            host[ntap + 2 * ((size_t)s * M + q)] = (float)c;
-            host[ntap + 2 * ((size_t)s * M + q) + 1] = (float)sn;
-        }
-    }
+    nsh::pfb::fill_twiddles(M, host.data() + ntap);
     // at most 37.75 KiB (38 656 bytes, M = 32 with 1024 taps; M = 64 with 1024 taps: 38 400)
     // the twiddles start ntap floats in, a multiple of 8 floats
     if (const int rc = p->upload(host.data(), host.size() * sizeof(float), "nsh_pfb_plan_create")) return rc;

@@ -91,6 +91,11 @@ SIGNATURES = {
     "nsh_pfb_tile": (_i, [_vp]),
     "nsh_pfb_kernel": (C.c_char_p, [_vp]),
     "nsh_pfb_channelizer_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_pfb_synth_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.POINTER(_vp)]),
+    "nsh_pfb_synth_plan_destroy": (_i, [_vp]),
+    "nsh_pfb_synth_tile": (_i, [_vp]),
+    "nsh_pfb_synth_kernel": (C.c_char_p, [_vp]),
+    "nsh_pfb_synthesizer_ccf": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "nsh_resamp_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, _i, C.POINTER(_vp)]),
     "nsh_resamp_plan_destroy": (_i, [_vp]),
     "nsh_resamp_tile": (_i, [_vp]),
@@ -338,6 +343,31 @@ class PfbPlan(_Plan):
         hist_out: ntaps-1 raw samples."""
         check(lib().nsh_pfb_channelizer_ccf(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y),
                                             n_out, stream_ptr(stream)), "nsh_pfb_channelizer_ccf")
+
+
+class PfbSynthPlan(_Plan):
+    """Critically sampled polyphase synthesis filterbank, the channelizer's counterpart (an inverse
+    DFT across the nchans channels of every item and nchans branch FIRs in one kernel); see
+    nsh_pfb_synthesizer_ccf."""
+
+    _destroy = "nsh_pfb_synth_plan_destroy"
+
+    def __init__(self, taps, nchans: int, device: int = 0):
+        t, arr = self._taps_arg(taps)
+        self.ntaps = int(t.size)
+        self.nchans = int(nchans)
+        h = C.c_void_p()
+        check(lib().nsh_pfb_synth_plan_create(device, arr, self.ntaps, self.nchans, C.byref(h)),
+              "nsh_pfb_synth_plan_create")
+        self._h = h
+        self.tile = lib().nsh_pfb_synth_tile(h)
+        self.kernel = lib().nsh_pfb_synth_kernel(h).decode()
+
+    def __call__(self, x, hist_in, hist_out, y, n_in: int, stream=None):
+        """n_in * nchans outputs from n_in items of nchans channels; hist_in (or None = zeros) /
+        hist_out: the ceil(ntaps / nchans) - 1 raw items before x."""
+        check(lib().nsh_pfb_synthesizer_ccf(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y),
+                                            n_in, stream_ptr(stream)), "nsh_pfb_synthesizer_ccf")
 
 
 class ResampPlan(_Plan):
