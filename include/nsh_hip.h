@@ -210,10 +210,22 @@ int nsh_fir_ccf(void* plan, const float* in, const float* hist_in, float* hist_o
  * north-star tolerance 1e-5). So quiet outputs that share a frame (8192 inputs at D = 16) with a
  * much louder burst are accurate to the burst's level, not their own
  * (tests/test_gpu_pfft.py::test_c5_mixed_amplitude_frame_relative_bound).
+ * The frame window of output m of a call is inputs [D (f V - Q), D (f V - Q) + 512 D), f = m / V,
+ * Q = ceil((len(heq) - 1) / D), V = 512 - Q (the call's history before input 0). The frame is scaled
+ * by an exact power of two taken from that window (k_fir_pfft2<16>) or, in k_fir_pfft<P,1>, from
+ * inputs [D (f - 1) V, D (f + 1) V), which add the V - Q rows before the window: a stretch there
+ * more than about 2^100 louder than the whole window pushes the window into fp32's subnormals.
+ * tests/test_gpu_pfft_taps.py holds every output to the bound above on full-size asymmetric taps,
+ * impulses, scale exponents from -110 to 125 and inf/NaN frames at three and four frames per workgroup.
  * Frames holding inf/NaN are computed by the staged chain itself (fp32 direct form, stage by
- * stage over the frame's window): their NaN and inf outputs are the chain's exactly (a one-stage
- * plan: the direct form on its taps; a chain whose first stage has decimation 1: the direct form
- * on heq, which can give +-inf where the chain's inf - inf gives NaN). */
+ * stage over the frame's window): their NaN and inf outputs are the chain's exactly. That holds for
+ * chains of 2 to 8 stages whose first two stage outputs over one window fit the kernel's image
+ * buffers: n1 + n2 <= 571 D, n1 = ceil(512 D / D_1), n2 = ceil(n1 / D_2) -- every chain that starts
+ * with a decimating stage, and e.g. (h, 1) -> (g, 16). Every other plan runs the fp32 direct form on
+ * heq for such frames, which can give +-inf where the chain's inf - inf gives NaN: a one-stage plan
+ * (heq is its taps), a chain of more than 8 stages, and a chain that does not fit, e.g.
+ * (h, 1) -> (g, 2) -> (k, 8), or (h, 1) -> (g, 8) at D = 8
+ * (tests/test_gpu_pfft_taps.py::test_nonfinite_plan_variants). */
 int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const int* ntaps, const int* decims,
                                 int nstages, void** plan);
 int nsh_fir_cascade_plan_destroy(void* plan);

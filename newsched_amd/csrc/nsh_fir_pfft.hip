@@ -404,18 +404,26 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
         }
     }
 
-    // first window: rows [f0 V, f0 V + M), history-aware
-    unsigned m = 0;
+    // first window: rows [f0 V, f0 V + M), history-aware. Its maximum in two parts, the new rows in
+    // frame f0's slot and the Q overlap rows before them in the other one (as if frame f0 - 1 had left
+    // it): frame f0 + 1, whose window no longer holds those Q rows, must not take its scale from them
+    // (kept in one slot, a 2^125 stretch before the workgroup's range flushed a 2^-110 frame f0 + 1).
+    unsigned m = 0, mo = 0;
     for (int i = tid; i < M * P; i += NT) {
         const float2 xv = virt(a.x, a.hist_in, (int64_t)P * (f0 * V - Q) + i, n_in, L);
         const int s = (int)((f0 * V + i / P) & (M - 1));
         ring[ring_at<P>(s, i % P)] = cf{ xv.x, xv.y };
-        m = max(m, max(absbits(xv.x), absbits(xv.y)));
+        const unsigned b = max(absbits(xv.x), absbits(xv.y));
+        if (i < P * Q)
+            mo = max(mo, b);
+        else
+            m = max(m, b);
     }
     m = nsh::wave_umax(m);
+    mo = nsh::wave_umax(mo);
     if (j == 0) {
         mx[(f0 & 1) * WAVES + w] = m;
-        mx[((f0 + 1) & 1) * WAVES + w] = 0u;
+        mx[((f0 + 1) & 1) * WAVES + w] = mo;
     }
     float4 pre[S::PRE];
     load_rows<P, PW>(pre, a, n_in, f0 + 1);
@@ -438,7 +446,7 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
 #pragma unroll
         for (int r = 1; r < 8; ++r) asm volatile("" : "+v"(t2[r]), "+v"(t3[r]));
         // the window's largest magnitude: this frame's new rows and the previous frame's (which
-        // hold the overlap; the first window's slot covers all of it)
+        // hold the overlap; before the first window, the overlap rows alone)
         const unsigned wm = nsh::wave_umax(j < 2 * WAVES ? mx[j] : 0u); // one LDS read, DPP max
         const bool bad = wm >= 0x7f800000u; // inf or NaN in the window
         int ks = 127 - (int)(wm >> 23);      // max * 2^ks in [1, 2)
@@ -1159,7 +1167,8 @@ int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const in
     std::vector<float> hf(heq.begin(), heq.end());
     // the stages for non-finite frames: stage outputs within one window ping-pong between two
     // buffers in the wave images (stage 1's, then stage 2's size); a chain that does not fit (a
-    // leading decim-1 stage), or has one stage, uses the composite direct form instead
+    // leading decim-1 stage, unless the second stage decimates by 16), has one stage or more than
+    // MAX_STAGES uses the composite direct form instead
     std::vector<float> st;
     if (nstages >= 2 && nstages <= MAX_STAGES) {
         const int n1 = (D * M - 1) / decims[0] + 1, n2 = (n1 - 1) / decims[1] + 1;
