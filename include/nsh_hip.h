@@ -437,6 +437,43 @@ int nsh_arb_resamp_ccf(void* plan, const float* in, int64_t n_in, const float* h
 int nsh_fft1024_c2c(const float* in, float* out, int64_t nframes, int inverse, void* stream);
 int nsh_channelizer1024(const float* in, float* out, const float* w, int64_t nframes, void* stream);
 
+/* ---- FFT plan (fft_vcc of any power-of-two size 16..8192, windowed and shifted) --------
+ * Frames of fft_size complex samples, forward or inverse, unnormalised both ways, with an optional
+ * real window of fft_size floats (host; copied) on the input and an optional half-frame shift, in
+ * one launch: every sample crosses HBM once each way. With w[n] = 1 when window_host is NULL:
+ *   forward  X[k] = sum_n x[n] w[n] e^{-2 pi i kn/N};  shift: out[k] = X[(k + N/2) mod N]
+ *   inverse  y[n] = x[n] w[n] (the window indexed by the input position as it arrives);
+ *            shift: y'[n] = y[(n + N/2) mod N];  out[m] = sum_n y'[n] e^{+2 pi i mn/N}
+ *            (= N * numpy.fft.ifft of y').
+ * The window product is one fp32 multiply per component, the shift an index change on the store
+ * (forward) or the load (inverse): the shifted output is bit-identical to the swapped halves of the
+ * unshifted one, and an all-ones window to none. A plan of size 1024 without window and shift runs
+ * the kernel of nsh_fft1024_c2c (same bits).
+ * nsh_fft_c2c runs on the current device, which must be the plan's. in and out need only 8-byte
+ * alignment (results are bit-identical to the 16-byte aligned call); they must not alias. Exactly
+ * nframes * fft_size samples are read and written for any nframes >= 1.
+ * Frames are independent: a frame's output depends on that frame's samples alone, bit for bit,
+ * whatever the batch size, the frame's slot in its wave or workgroup (nsh_fft_tile frames share a
+ * workgroup, up to 64 a wave) and the grid cap; a non-finite sample makes all fft_size outputs of
+ * its own frame non-finite and touches no other frame.
+ * Scaling the input (or the window) by a power of two scales the output by it exactly, as long as
+ * nothing overflows or turns subnormal.
+ * nsh_fft_plan_grid_cap bounds the workgroups of the grid-stride walk over the frames (0 restores
+ * the default); the output does not depend on it.
+ * Refused before any HIP call: an fft_size that is not a power of two in [16, 8192], a NULL plan
+ * out-pointer, a non-finite window entry, a NULL plan / in / out at run time, in == out, a negative
+ * cap. nframes <= 0 returns 0 and launches nothing, whatever the other arguments. An armed
+ * nsh_time_next_launch pair is taken by the one launch (dropped when nothing is launched).
+ * Measured: DESIGN.md section 4.7. */
+int nsh_fft_plan_create(int dev, int fft_size, int inverse, const float* window_host /* NULL: none */, int shift,
+                        void** plan);
+int nsh_fft_plan_destroy(void* plan);                 /* NULL: 0 */
+int nsh_fft_plan_size(void* plan);                    /* fft_size; 0 for NULL */
+int nsh_fft_tile(void* plan);                         /* frames per workgroup; 0 for NULL */
+const char* nsh_fft_kernel(void* plan);               /* e.g. "k_fft<4096, false, false>"; "" for NULL */
+int nsh_fft_plan_grid_cap(void* plan, int max_workgroups);
+int nsh_fft_c2c(void* plan, const float* in, float* out, int64_t nframes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

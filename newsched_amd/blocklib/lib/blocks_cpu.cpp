@@ -1,5 +1,6 @@
 // CPU block implementations (reference blocklib/blocks/lib/*.cpp semantics).
 #include <gnuradio/blocklib/blocks/arith.hpp>
+#include <gnuradio/blocklib/blocks/fft.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
@@ -421,6 +422,53 @@ work_return_code_t pfb_synthesizer_ccf::work(std::vector<block_work_input>& in, 
     std::memmove(_ext.data(), _ext.data() + n_samp, H * sizeof(gr_complex)); // the last Q-1 raw items
     _ext.resize(H);
     out[0].n_produced = n_in * M;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- fft_vcc: radix-2 in double, rounded once ------------------------------------------------------
+fft_vcc::fft_vcc(size_t fft_size, bool forward, const std::vector<float>& window, bool shift)
+    : sync_block(forward ? "fft_vcc" : "ifft_vcc"), _fft_size(fft_size), _forward(forward), _shift(shift), _window(window)
+{
+    if (fft_size < 16 || fft_size > 8192 || (fft_size & (fft_size - 1)))
+        throw std::invalid_argument("fft_vcc: fft_size must be a power of two in [16, 8192]");
+    if (!window.empty() && window.size() != fft_size) throw std::invalid_argument("fft_vcc: the window must have fft_size entries");
+    _tw.resize(fft_size / 2);
+    for (size_t t = 0; t < fft_size / 2; ++t) {
+        const double a = (forward ? -2.0 : 2.0) * M_PI * (double)t / (double)fft_size;
+        _tw[t] = { std::cos(a), std::sin(a) };
+    }
+    _a.resize(fft_size);
+}
+
+work_return_code_t fft_vcc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const size_t N = _fft_size, H = N / 2;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    size_t bits = 0;
+    while (((size_t)1 << bits) < N) ++bits;
+    for (int f = 0; f < out[0].n_items; ++f, x += N, y += N) {
+        // window (fp32 products), the inverse's input shift and the bit reversal, in one placement
+        for (size_t n = 0; n < N; ++n) {
+            const size_t src = !_forward && _shift ? n ^ H : n;
+            const float w = _window.empty() ? 1.f : _window[src];
+            size_t rev = 0;
+            for (size_t b = 0; b < bits; ++b) rev |= ((n >> b) & 1) << (bits - 1 - b);
+            _a[rev] = { (double)(x[src].real() * w), (double)(x[src].imag() * w) };
+        }
+        for (size_t len = 2; len <= N; len <<= 1)
+            for (size_t i = 0; i < N; i += len)
+                for (size_t k = 0; k < len / 2; ++k) {
+                    const std::complex<double> u = _a[i + k], v = _a[i + k + len / 2] * _tw[k * (N / len)];
+                    _a[i + k] = u + v;
+                    _a[i + k + len / 2] = u - v;
+                }
+        for (size_t k = 0; k < N; ++k) {
+            const std::complex<double> v = _a[_forward && _shift ? k ^ H : k];
+            y[k] = gr_complex((float)v.real(), (float)v.imag());
+        }
+    }
+    out[0].n_produced = out[0].n_items;
     return work_return_code_t::WORK_OK;
 }
 

@@ -596,15 +596,35 @@ work_return_code_t pfb_arb_resampler_ccf::work(std::vector<block_work_input>& in
 }
 
 // ---- FFT ---------------------------------------------------------------------------
-fft_vcc::fft_vcc(size_t fft_size, bool forward) : sync_block(forward ? "fft_vcc (hip)" : "ifft_vcc (hip)"), _forward(forward)
+fft_vcc::fft_vcc(size_t fft_size, bool forward, const std::vector<float>& window, bool shift)
+    : sync_block(forward ? "fft_vcc (hip)" : "ifft_vcc (hip)"), _fft_size(fft_size), _forward(forward), _shift(shift), _window(window)
 {
-    if (fft_size != 1024) throw std::invalid_argument("hip::fft_vcc: only 1024-point transforms are implemented");
+    if (fft_size < 16 || fft_size > 8192 || (fft_size & (fft_size - 1)))
+        throw std::invalid_argument("hip::fft_vcc: fft_size must be a power of two in [16, 8192]");
+    if (!window.empty() && window.size() != fft_size)
+        throw std::invalid_argument("hip::fft_vcc: the window must have fft_size entries");
+}
+fft_vcc::~fft_vcc() { nsh_fft_plan_destroy(_plan); }
+bool fft_vcc::start()
+{
+    const int dev = current_device();
+    if (_plan && _plan_dev != dev) {
+        nsh_fft_plan_destroy(_plan);
+        _plan = nullptr;
+    }
+    if (!_plan) {
+        check(nsh_fft_plan_create(dev, (int)_fft_size, _forward ? 0 : 1, _window.empty() ? nullptr : _window.data(), _shift ? 1 : 0,
+                                  &_plan),
+              "hip::fft_vcc plan");
+        _plan_dev = dev;
+    }
+    return sync_block::start();
 }
 
 work_return_code_t fft_vcc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
 {
-    check(nsh_fft1024_c2c((const float*)in[0].buffer->read_ptr(), (float*)out[0].buffer->write_ptr(), out[0].n_items,
-                          _forward ? 0 : 1, current_stream()),
+    check(nsh_fft_c2c(_plan, (const float*)in[0].buffer->read_ptr(), (float*)out[0].buffer->write_ptr(), out[0].n_items,
+                      current_stream()),
           "hip::fft_vcc");
     out[0].n_produced = out[0].n_items;
     return work_return_code_t::WORK_OK;

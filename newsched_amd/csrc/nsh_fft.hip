@@ -20,8 +20,7 @@
 // by W in registers and runs the inverse transform directly: pass 3 leaves lane j holding
 // indices j + 64 m (m < 16), exactly pass 1's input layout, so a frame crosses HBM once
 // each way (16 B/sample instead of 48 B unfused) and LDS twice per transform.
-#include "nsh_common.hpp"
-#include "nsh_cplx.hpp"
+#include "nsh_fft_shared.hpp"
 
 #include <cmath>
 #include <mutex>
@@ -36,6 +35,10 @@ using nsh::cf;
 using nsh::cmulw;
 using nsh::dft4;
 using nsh::rot;
+using nsh::fft::conj_if;
+using nsh::fft::dft16;
+using nsh::fft::frame_grid;
+using nsh::fft::pad;
 
 // the channelizer's spectrum multiply: nsh_mul_const_vcc's two-product rounding exactly, so
 // the fused channelizer stays bit-identical to fft -> multiply_const_vcc -> ifft
@@ -45,62 +48,7 @@ __device__ __forceinline__ cf cmul_rn(cf a, cf b)
     const cf u = a.yy * b.yx; // (ay by, ay bx)
     return t + u * cf{ -1.f, 1.f }; // (ax bx - ay by, ax by + ay bx): exact sign flip, one rounding
 }
-// W_16^m, m = 0..9 (forward; conjugated for the inverse)
-template <bool INV>
-__device__ __forceinline__ cf w16(int m)
-{
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508978f, R2 = 0.70710678118654757f;
-    cf w;
-    switch (m) {
-    case 1: w = cf{ C1, -S1 }; break;
-    case 2: w = cf{ R2, -R2 }; break;
-    case 3: w = cf{ S1, -C1 }; break;
-    case 4: w = cf{ 0.f, -1.f }; break;
-    case 6: w = cf{ -R2, -R2 }; break;
-    case 9: w = cf{ -C1, S1 }; break;
-    default: w = cf{ 1.f, 0.f }; break;
-    }
-    if (INV) w.y = -w.y;
-    return w;
-}
-
-// In-place DFT16, natural order in and out: n = 4 n1 + n2, k = k1 + 4 k2,
-// X[k] = sum_n2 W_4^{n2 k2} W_16^{n2 k1} sum_n1 x[4 n1 + n2] W_4^{n1 k1}.
-template <bool INV>
-__device__ __forceinline__ void dft16(cf (&v)[16])
-{
-#pragma unroll
-    for (int n2 = 0; n2 < 4; ++n2) dft4<INV>(v[n2], v[n2 + 4], v[n2 + 8], v[n2 + 12]); // v[n2 + 4 k1] = Y[n2][k1]
-#pragma unroll
-    for (int n2 = 1; n2 < 4; ++n2)
-#pragma unroll
-        for (int k1 = 1; k1 < 4; ++k1) {
-            const int m = n2 * k1;
-            if (m == 4) // W_16^4 = -+i
-                v[n2 + 4 * k1] = rot<INV>(v[n2 + 4 * k1]);
-            else
-                v[n2 + 4 * k1] = cmulw(v[n2 + 4 * k1], w16<INV>(m));
-        }
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) dft4<INV>(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]); // v[4 k1 + k2] = X[k1 + 4 k2]
-    cf t[16];
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1)
-#pragma unroll
-        for (int k2 = 0; k2 < 4; ++k2) t[k1 + 4 * k2] = v[4 * k1 + k2];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = t[k];
-}
-
-constexpr int WLDS = N + N / 16; // one wave's padded image
-__device__ __forceinline__ int pad(int i) { return i + (i >> 4); }
-
-template <bool INV>
-__device__ __forceinline__ cf conj_if(cf w)
-{
-    if (INV) w.y = -w.y;
-    return w;
-}
+constexpr int WLDS = nsh::fft::padded(N); // one wave's padded image
 
 // The passes' twiddles, staged per workgroup. Read from the natural 1024-entry table (the default),
 // pass 2's W_1024^{4 k r} (k = lane & 15) puts the 16 lanes of a read group at stride 4 r entries --
@@ -117,10 +65,9 @@ __device__ __forceinline__ cf conj_if(cf w)
 constexpr int T2N = 16 * 16, T3N = 3 * 256, TWN = NSH_FFT_TW_READORDER ? T2N + T3N : N;
 __device__ __forceinline__ void stage_twiddles(cf* __restrict__ t, const float2* __restrict__ tw_g, int tid, int nt)
 {
+    if (!NSH_FFT_TW_READORDER) return nsh::fft::stage_table(t, tw_g, TWN, tid, nt);
     for (int i = tid; i < TWN; i += nt) {
-        int e = i;
-        if (NSH_FFT_TW_READORDER)
-            e = i < T2N ? (4 * (i & 15) * (i >> 4)) & (N - 1) : ((1 + (i - T2N) / 256) * ((i - T2N) & 255)) & (N - 1);
+        const int e = i < T2N ? (4 * (i & 15) * (i >> 4)) & (N - 1) : ((1 + (i - T2N) / 256) * ((i - T2N) & 255)) & (N - 1);
         t[i] = cf{ tw_g[e].x, tw_g[e].y };
     }
 }
@@ -179,24 +126,14 @@ __device__ __forceinline__ void fft_wave(cf (&v)[16], cf* __restrict__ img, cons
     for (int m = 0; m < 16; ++m) v[m] = o[m];
 }
 
-// Frame f of a stream of nframes frames by buffer loads/stores over that frame alone: a frame
-// past the end reads zeros and drops its stores, so the loop issues the same memory
-// instructions every iteration (no conditional prefetch) and the compiler's vmcnt waits stay
-// exact -- the next frame's loads remain in flight across this frame's transform and stores.
+// Frame f of a stream of nframes frames, lane j holding samples j + 64 m (nsh::fft::load16 / store16)
 __device__ __forceinline__ void load_frame16(cf (&v)[16], const float2* __restrict__ in, int64_t f, int64_t nframes)
 {
-    const int j = threadIdx.x & 63;
-    const __amdgpu_buffer_rsrc_t r = nsh::chunk_rsrc<N>(in, f, nframes * N);
-#pragma unroll
-    for (int m = 0; m < 16; ++m)
-        v[m] = __builtin_bit_cast(cf, __builtin_amdgcn_raw_buffer_load_b64(r, (j + 64 * m) * 8, 0, nsh::AUX_LD));
+    nsh::fft::load16<N>(v, in, f, nframes * N, nsh::fft::lane64{ (int)(threadIdx.x & 63) });
 }
 __device__ __forceinline__ void store_frame16(const cf (&v)[16], float2* __restrict__ out, int64_t f, int64_t nframes)
 {
-    const int j = threadIdx.x & 63;
-    const __amdgpu_buffer_rsrc_t r = nsh::chunk_rsrc<N>(out, f, nframes * N);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) nsh::buf_store_f2(r, (j + 64 * m) * 8, v[m]);
+    nsh::fft::store16<N>(v, out, f, nframes * N, nsh::fft::lane64{ (int)(threadIdx.x & 63) });
 }
 
 constexpr int FPW = NT / 64; // frames (waves) per workgroup
@@ -290,10 +227,7 @@ int twiddles(int dev, const float2** tw)
     if (dev < 0 || dev >= (int)g_tw.size()) return nsh::fail_msg("fft: bad device");
     if (!g_tw[dev]) {
         std::vector<float2> h(N);
-        for (int t = 0; t < N; ++t) {
-            const double a = -2.0 * M_PI * (double)t / (double)N;
-            h[t] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
+        for (int t = 0; t < N; ++t) h[t] = nsh::fft::twiddle(t, N);
         float2* d = nullptr;
         NSH_CK(hipMalloc(&d, N * sizeof(float2)));
         NSH_CK(hipMemcpy(d, h.data(), N * sizeof(float2), hipMemcpyHostToDevice));
@@ -317,12 +251,6 @@ int twiddles(int dev, const float2** tw)
 #ifndef NSH_CHAN_CAP
 #define NSH_CHAN_CAP (65536 / NSH_CHAN_FPW) // probe builds with NSH_CHAN_FPW != 4: the same frames per workgroup step
 #endif
-unsigned frame_grid(int64_t nframes, int fw, int64_t cap)
-{
-    const int64_t groups = (nframes + fw - 1) / fw;
-    return (unsigned)(groups < cap ? groups : cap);
-}
-
 } // namespace
 
 extern "C" {
@@ -333,18 +261,7 @@ int nsh_fft1024_c2c(const float* in, float* out, int64_t nframes, int inverse, v
     if (nframes <= 0) return 0;
     if (!in || !out) return nsh::fail_msg("nsh_fft1024_c2c: null pointer");
     if (in == out) return nsh::fail_msg("nsh_fft1024_c2c: in-place not supported");
-    int dev = 0;
-    NSH_CK(hipGetDevice(&dev));
-    const float2* tw = nullptr;
-    if (int rc = twiddles(dev, &tw)) return rc;
-    if (inverse)
-        nsh::launch(k_fft1024<true>, dim3(frame_grid(nframes, FPW, NSH_FFT_CAP)), dim3(NT), 0, nsh::S(stream),
-                           (const float2*)in, (float2*)out, nframes, tw);
-    else
-        nsh::launch(k_fft1024<false>, dim3(frame_grid(nframes, FPW, NSH_FFT_CAP)), dim3(NT), 0, nsh::S(stream),
-                           (const float2*)in, (float2*)out, nframes, tw);
-    NSH_CK_LAUNCH("nsh_fft1024_c2c");
-    return 0;
+    return nsh::fft::fft1024_launch((const float2*)in, (float2*)out, nframes, inverse != 0, 0, nsh::S(stream), "nsh_fft1024_c2c");
 }
 
 int nsh_channelizer1024(const float* in, float* out, const float* w, int64_t nframes, void* stream)
@@ -364,3 +281,18 @@ int nsh_channelizer1024(const float* in, float* out, const float* w, int64_t nfr
 }
 
 } // extern "C"
+
+int nsh::fft::fft1024_launch(const float2* in, float2* out, int64_t nframes, bool inverse, int cap, hipStream_t s, const char* what)
+{
+    int dev = 0;
+    NSH_CK(hipGetDevice(&dev));
+    const float2* tw = nullptr;
+    if (int rc = twiddles(dev, &tw)) return rc;
+    const dim3 grid(frame_grid(nframes, FPW, cap > 0 ? cap : NSH_FFT_CAP));
+    if (inverse)
+        nsh::launch(k_fft1024<true>, grid, dim3(NT), 0, s, in, out, nframes, tw);
+    else
+        nsh::launch(k_fft1024<false>, grid, dim3(NT), 0, s, in, out, nframes, tw);
+    NSH_CK_LAUNCH(what);
+    return 0;
+}

@@ -113,6 +113,13 @@ SIGNATURES = {
     "nsh_arb_resamp_ccf": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _u64, _vp]),
     "nsh_fft1024_c2c": (_i, [_vp, _vp, _i64, _i, _vp]),
     "nsh_channelizer1024": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "nsh_fft_plan_create": (_i, [_i, _i, _i, C.POINTER(_f), _i, C.POINTER(_vp)]),
+    "nsh_fft_plan_destroy": (_i, [_vp]),
+    "nsh_fft_plan_size": (_i, [_vp]),
+    "nsh_fft_tile": (_i, [_vp]),
+    "nsh_fft_kernel": (C.c_char_p, [_vp]),
+    "nsh_fft_plan_grid_cap": (_i, [_vp, _i]),
+    "nsh_fft_c2c": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -260,6 +267,41 @@ class _Plan:
             self.close()
         except Exception:
             pass
+
+
+class FftPlan(_Plan):
+    """FFT of fft_size = 2^k points (16..8192), forward or inverse, unnormalised, with an optional
+    real window on the input and an optional half-frame shift, in one launch; see nsh_fft_c2c."""
+
+    _destroy = "nsh_fft_plan_destroy"
+
+    def __init__(self, fft_size: int, inverse: bool = False, window=None, shift: bool = False, device: int = 0):
+        self.fft_size = int(fft_size)
+        self.inverse = bool(inverse)
+        self.shift = bool(shift)
+        arr = None
+        if window is not None:
+            w, arr = self._taps_arg(window)
+            if w.size != self.fft_size:
+                raise NshError(f"FftPlan: the window has {w.size} entries, fft_size is {self.fft_size}")
+        h = C.c_void_p()
+        check(lib().nsh_fft_plan_create(device, self.fft_size, 1 if inverse else 0, arr, 1 if shift else 0, C.byref(h)),
+              "nsh_fft_plan_create")
+        self._h = h
+        self.tile = lib().nsh_fft_tile(h)
+        self.kernel = lib().nsh_fft_kernel(h).decode()
+
+    def grid_cap(self, max_workgroups: int = 0):
+        """At most max_workgroups workgroups per launch (0: the default); the output does not depend on it."""
+        check(lib().nsh_fft_plan_grid_cap(self._h, int(max_workgroups)), "nsh_fft_plan_grid_cap")
+
+    def __call__(self, x, y, nframes: int, stream=None):
+        check(lib().nsh_fft_c2c(self._h, ptr(x), ptr(y), nframes, stream_ptr(stream)), "nsh_fft_c2c")
+
+
+def fft_c2c(plan: FftPlan, x, y, nframes: int, stream=None):
+    """y = the plan's transform of nframes frames of x (device tensors, complex64 or float32 views)."""
+    plan(x, y, nframes, stream)
 
 
 class FirPlan(_Plan):

@@ -206,11 +206,13 @@ fusion_result fuse_channelizer(flat_graph_sptr fg)
     std::set<block*> used;
     for (auto& b : fg->calc_used_blocks()) {
         auto f1 = std::dynamic_pointer_cast<fft_vcc>(b);
-        if (!f1 || !f1->forward() || used.count(b.get())) continue;
+        // the fused kernel is the plain 1024-point pair: no window, no shift
+        auto plain1024 = [](const fft_vcc& f) { return f.fft_size() == 1024 && f.window().empty() && !f.shift(); };
+        if (!f1 || !f1->forward() || !plain1024(*f1) || used.count(b.get())) continue;
         auto m = std::dynamic_pointer_cast<multiply_const_vcc>(next(b));
         if (!m || m->k().size() != 1024) continue;
         auto f2 = std::dynamic_pointer_cast<fft_vcc>(next(m));
-        if (!f2 || f2->forward() || used.count(f2.get())) continue;
+        if (!f2 || f2->forward() || !plain1024(*f2) || used.count(f2.get())) continue;
         auto c = channelizer_vcc::make(m->k());
         c->set_tag_propagation_policy(b->tag_propagation_policy());
         c->set_alias("fused(" + b->alias() + ".." + f2->alias() + ")");
