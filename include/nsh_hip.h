@@ -474,6 +474,54 @@ const char* nsh_fft_kernel(void* plan);               /* e.g. "k_fft<4096, false
 int nsh_fft_plan_grid_cap(void* plan, int max_workgroups);
 int nsh_fft_c2c(void* plan, const float* in, float* out, int64_t nframes, void* stream);
 
+/* ---- fft_filter_ccc: FIR filter with complex taps by overlap-save (GNU Radio's fft_filter_ccc) ----
+ * h = taps_host: ntaps = L complex fp32 taps as (re, im) pairs, 1 <= L <= 4096; x the complex fp32
+ * input stream; decimation 1:
+ *   y[n] = sum_{k<L} h[k] * x[n-k]
+ * History as nsh_fir_ccf: hist_in = the L-1 raw samples before in[0] (NULL = zeros); hist_out
+ * receives the last L-1 raw samples of hist_in ++ in bit-exactly, must not alias hist_in and is
+ * required when L > 1.
+ * Frames: N = fft_size in {1024, 2048, 4096, 8192} with L <= N/2; 0 lets the plan choose: 1024 up
+ * to 256 taps, 2048 up to 512, 4096 up to 2048, 8192 above (the smallest N >= 4 * pow2ceil(L) up to
+ * 4096, the smallest N >= 2 * pow2ceil(L) beyond; pow2ceil: the next power of two at or above).
+ * V = N - (L-1) valid outputs per frame: frame f of a call owns out[fV, (f+1)V) up to n and reads
+ * the window of inputs [fV-(L-1), fV-(L-1)+N); window positions below 0 come from the history (or
+ * are zeros), positions at or past n are zeros, nothing at or past out[n] is stored. One launch of
+ * k_fft_filter<N> per call: window -> forward FFT -> times Hs -> inverse FFT -> store of the valid
+ * part, with
+ *   Hs[k] = (1/N) sum_{n<L} h[n] e^{-2 pi i kn/N}
+ * computed in double on the host and rounded once to fp32 (the 1/N is a power of two: exact).
+ * nsh_fft_filter_tile frames share a workgroup step.
+ * Rounding: an output's rounding depends on its frame, and so on how the stream is cut into calls
+ * (a call's frames start at its in[0]) -- unlike the direct-form kernels, two chained calls are not
+ * bit-identical to one; only hist_out is bit-exact. Within a call a frame's outputs depend on its
+ * window alone, bit for bit, whatever follows it, the workgroup that runs it and the grid cap.
+ * Accuracy: for output m in frame f, with y_ref the float64 convolution,
+ *   |y - y_ref| <= 1e-5 |y_ref| + 1e-6 * max|x over frame f's window| * sum_k |h[k]|
+ * Non-finite samples: a non-finite sample makes non-finite every output of every frame whose window
+ * holds it (two frames where windows overlap), and touches no other frame.
+ * in, out and the histories need only 8-byte alignment.
+ * Refused before any HIP call, in this order. nsh_fft_filter_plan_create: a NULL taps_host or plan
+ * out-pointer; ntaps outside [1, 4096]; a non-finite tap; an fft_size that is neither 0 nor one of
+ * the four sizes; ntaps > fft_size / 2. nsh_fft_filter_ccc: n <= 0 returns 0 and launches nothing,
+ * whatever the other arguments; then a NULL in or out; in == out; hist_out aliasing hist_in; a
+ * NULL plan; a missing hist_out when ntaps > 1. nsh_fft_filter_grid_cap: a negative cap, then a NULL
+ * plan; it bounds the workgroups of the grid-stride walk over the frames (0 restores the default)
+ * and the output does not depend on it. An armed nsh_time_next_launch pair is taken by the one
+ * launch (dropped when nothing is launched). Runs on the current device, which must be the plan's.
+ * Measured: DESIGN.md section 4.8. */
+int nsh_fft_filter_plan_create(int dev, const float* taps_host /* ntaps (re, im) pairs */, int ntaps,
+                               int fft_size /* 0: chosen by the plan */, void** plan);
+int nsh_fft_filter_plan_destroy(void* plan);          /* NULL: 0 */
+int nsh_fft_filter_fft_size(void* plan);              /* N; 0 for NULL */
+int nsh_fft_filter_valid(void* plan);                 /* V = N - (ntaps - 1); 0 for NULL */
+int nsh_fft_filter_history(void* plan);               /* ntaps - 1; 0 for NULL */
+int nsh_fft_filter_tile(void* plan);                  /* frames per workgroup step; 0 for NULL */
+const char* nsh_fft_filter_kernel(void* plan);        /* e.g. "k_fft_filter<2048>"; "" for NULL */
+int nsh_fft_filter_grid_cap(void* plan, int max_workgroups);
+int nsh_fft_filter_ccc(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

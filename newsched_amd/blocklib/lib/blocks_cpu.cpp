@@ -1,6 +1,7 @@
 // CPU block implementations (reference blocklib/blocks/lib/*.cpp semantics).
 #include <gnuradio/blocklib/blocks/arith.hpp>
 #include <gnuradio/blocklib/blocks/fft.hpp>
+#include <gnuradio/blocklib/blocks/fft_filter.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
@@ -567,6 +568,43 @@ work_return_code_t pfb_arb_resampler_ccf::work(std::vector<block_work_input>& in
     if (s.n_out == 0 && s.n_consumed > 0) ++_advances;
     out[0].n_produced = (int)s.n_out;
     in[0].n_consumed = (int)s.n_consumed;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- fft_filter_ccc: the direct form in double ---------------------------------------------------
+fft_filter_ccc::fft_filter_ccc(const std::vector<gr_complex>& taps) : sync_block("fft_filter_ccc"), _taps(taps)
+{
+    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("fft_filter_ccc: 1 to 4096 taps");
+    for (auto& t : taps)
+        if (!std::isfinite(t.real()) || !std::isfinite(t.imag())) throw std::invalid_argument("fft_filter_ccc: a tap is not finite");
+}
+
+bool fft_filter_ccc::start()
+{
+    _ext.assign(_taps.size() - 1, gr_complex(0, 0)); // zero history at stream start
+    return block::start();
+}
+
+work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const size_t n = (size_t)out[0].n_items, L = _taps.size();
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    if (_ext.size() < L - 1) _ext.assign(L - 1, gr_complex(0, 0)); // not started: zeros
+    _ext.resize(L - 1 + n);
+    std::memcpy(_ext.data() + (L - 1), in[0].buffer->read_ptr(), n * sizeof(gr_complex));
+    for (size_t i = 0; i < n; ++i) {
+        const gr_complex* x = _ext.data() + (L - 1) + i; // x[-k] = sample i - k
+        double re = 0, im = 0;
+        for (size_t k = 0; k < L; ++k) {
+            const double hr = _taps[k].real(), hi = _taps[k].imag(), xr = (x - k)->real(), xi = (x - k)->imag();
+            re += hr * xr - hi * xi;
+            im += hr * xi + hi * xr;
+        }
+        y[i] = gr_complex((float)re, (float)im);
+    }
+    std::memmove(_ext.data(), _ext.data() + n, (L - 1) * sizeof(gr_complex)); // the last L-1 inputs
+    _ext.resize(L - 1);
+    out[0].n_produced = (int)n;
     return work_return_code_t::WORK_OK;
 }
 

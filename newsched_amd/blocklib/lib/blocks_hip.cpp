@@ -4,6 +4,7 @@
 #include <gnuradio/blocklib/hip/arith.hpp>
 #include <gnuradio/blocklib/hip/copy.hpp>
 #include <gnuradio/blocklib/hip/fft.hpp>
+#include <gnuradio/blocklib/hip/fft_filter.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_cascade_ccf.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
@@ -656,6 +657,62 @@ work_return_code_t channelizer_vcc::work(std::vector<block_work_input>& in, std:
     out[0].n_produced = out[0].n_items;
     return work_return_code_t::WORK_OK;
 }
+
+// ---- overlap-save FIR with complex taps ---------------------------------------------------
+fft_filter_ccc::fft_filter_ccc(const std::vector<gr_complex>& taps, size_t fft_size, const char* name)
+    : sync_block(name), _taps(taps), _fft_size(fft_size), _state("hip::fft_filter_ccc", nsh_fft_filter_plan_destroy),
+      _ev("hip::fft_filter_ccc")
+{
+    // what nsh_fft_filter_plan_create refuses, in its order
+    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("hip::fft_filter_ccc: 1 to 4096 taps");
+    for (auto& t : taps)
+        if (!std::isfinite(t.real()) || !std::isfinite(t.imag()))
+            throw std::invalid_argument("hip::fft_filter_ccc: a tap is not finite");
+    if (fft_size != 0 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096 && fft_size != 8192)
+        throw std::invalid_argument("hip::fft_filter_ccc: fft_size must be 0, 1024, 2048, 4096 or 8192");
+    if (fft_size && taps.size() > fft_size / 2)
+        throw std::invalid_argument("hip::fft_filter_ccc: at most fft_size / 2 taps");
+}
+
+fft_filter_ccc::~fft_filter_ccc() = default;
+
+size_t fft_filter_ccc::fft_size() const { return _state.plan() ? (size_t)nsh_fft_filter_fft_size(_state.plan()) : _fft_size; }
+std::string fft_filter_ccc::kernel() const { return _state.plan() ? nsh_fft_filter_kernel(_state.plan()) : std::string(); }
+
+bool fft_filter_ccc::start()
+{
+    const int dev = current_device();
+    if (_state.on_other_device(dev)) _ev.release(); // the events belong to the old device too
+    _state.prepare(dev, [this](int d, void** plan) {
+        check(nsh_fft_filter_plan_create(d, reinterpret_cast<const float*>(_taps.data()), (int)_taps.size(), (int)_fft_size, plan),
+              "hip::fft_filter_ccc plan");
+        return _taps.size() - 1;
+    });
+    _state.begin_run(current_stream()); // a fresh stream: the first call reads a null (zero) history
+    _ev.reuse();
+    _timed_samples = 0;
+    return sync_block::start();
+}
+
+work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n = out[0].n_items;
+    void* s = current_stream();
+    if (_timing) _ev.arm(s);
+    check(nsh_fft_filter_ccc(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                             (float*)out[0].buffer->write_ptr(), n, s),
+          "hip::fft_filter_ccc");
+    if (_timing) {
+        _ev.recorded(s);
+        _timed_samples += (uint64_t)n;
+    }
+    _state.flip();
+    ++_launches;
+    out[0].n_produced = n;
+    return work_return_code_t::WORK_OK;
+}
+
+double fft_filter_ccc::kernel_ms() { return _ev.sum_ms(); }
 
 // ---- synthetic source ----------------------------------------------------------------
 work_return_code_t synth_source::work(std::vector<block_work_input>&, std::vector<block_work_output>& out)

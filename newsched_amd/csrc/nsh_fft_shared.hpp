@@ -1,5 +1,6 @@
 // The pieces every FFT kernel of libnsh_hip.so is built from (k_fft1024 and k_chan1024 in
-// nsh_fft.hip, k_fft<N> in nsh_fft_plan.hip): the register DFT16, the padded LDS image, the
+// nsh_fft.hip, k_fft<N> in nsh_fft_plan.hip, k_fft_filter<N> in nsh_fft_filter.hip; the last two
+// share the team transform of nsh_fft_team.hpp on top of this file): the register DFT16, the padded LDS image, the
 // conjugation switch, twiddle staging and the 16-samples-per-lane buffer loads and stores.
 // gfx950 only.
 #pragma once

@@ -120,6 +120,15 @@ SIGNATURES = {
     "nsh_fft_kernel": (C.c_char_p, [_vp]),
     "nsh_fft_plan_grid_cap": (_i, [_vp, _i]),
     "nsh_fft_c2c": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "nsh_fft_filter_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.POINTER(_vp)]),
+    "nsh_fft_filter_plan_destroy": (_i, [_vp]),
+    "nsh_fft_filter_fft_size": (_i, [_vp]),
+    "nsh_fft_filter_valid": (_i, [_vp]),
+    "nsh_fft_filter_history": (_i, [_vp]),
+    "nsh_fft_filter_tile": (_i, [_vp]),
+    "nsh_fft_filter_kernel": (C.c_char_p, [_vp]),
+    "nsh_fft_filter_grid_cap": (_i, [_vp, _i]),
+    "nsh_fft_filter_ccc": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -302,6 +311,37 @@ class FftPlan(_Plan):
 def fft_c2c(plan: FftPlan, x, y, nframes: int, stream=None):
     """y = the plan's transform of nframes frames of x (device tensors, complex64 or float32 views)."""
     plan(x, y, nframes, stream)
+
+
+class FftFilterPlan(_Plan):
+    """FIR filter with complex taps by overlap-save in one launch (window -> FFT -> times the taps'
+    spectrum -> inverse FFT -> valid part); see nsh_fft_filter_ccc. fft_size 0: chosen by the plan."""
+
+    _destroy = "nsh_fft_filter_plan_destroy"
+
+    def __init__(self, taps, fft_size: int = 0, device: int = 0):
+        import numpy as np
+
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64))
+        self.ntaps = int(t.size)
+        h = C.c_void_p()
+        check(lib().nsh_fft_filter_plan_create(device, t.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)),
+                                               self.ntaps, int(fft_size), C.byref(h)), "nsh_fft_filter_plan_create")
+        self._h = h
+        self.fft_size = lib().nsh_fft_filter_fft_size(h)
+        self.valid = lib().nsh_fft_filter_valid(h)
+        self.hist_len = lib().nsh_fft_filter_history(h)
+        self.tile = lib().nsh_fft_filter_tile(h)
+        self.kernel = lib().nsh_fft_filter_kernel(h).decode()
+
+    def grid_cap(self, max_workgroups: int = 0):
+        """At most max_workgroups workgroups per launch (0: the default); the output does not depend on it."""
+        check(lib().nsh_fft_filter_grid_cap(self._h, int(max_workgroups)), "nsh_fft_filter_grid_cap")
+
+    def __call__(self, x, hist_in, hist_out, y, n: int, stream=None):
+        """n outputs from n inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw samples."""
+        check(lib().nsh_fft_filter_ccc(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n,
+                                       stream_ptr(stream)), "nsh_fft_filter_ccc")
 
 
 class FirPlan(_Plan):
