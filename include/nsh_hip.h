@@ -522,6 +522,55 @@ int nsh_fft_filter_grid_cap(void* plan, int max_workgroups);
 int nsh_fft_filter_ccc(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n,
                        void* stream);
 
+/* ---- psd_vcf: windowed FFT, |X|^2 and the sum over K frames (fft_vcc -> complex_to_mag_squared ->
+ * integrate_ff -> nlog10_ff) in one pass over the input ----
+ * N = fft_size, a power of two in [16, 8192]; K = navg in [1, 65536]; w = window_host, N floats
+ * (host; copied; NULL: none); scale finite and > 0 (1/K for the mean, 1/(K sum w^2) for a density).
+ * Output vector j takes the frames f = jK .. jK+K-1 of the input, frame f being samples fN .. fN+N-1
+ * (frames do not overlap):
+ *   X_f[k]   = sum_n x_f[n] w[n] e^{-2 pi i kn/N}     exactly as a forward nsh_fft_c2c plan with w
+ *   P_j[k]   = scale * sum_f |X_f[k]|^2
+ *   out_j[k] = P_j[k ^ (shift ? N/2 : 0)],  or 10 * log10f of that value when db is set (a zero sum
+ *              gives -inf: the documented result, not an error).
+ * nsh_psd_cf reads nvec * K * N complex samples and writes nvec * N floats; in needs 8-byte and out
+ * 4-byte alignment; they must not alias. Every sample is read once: 8 + 4/K bytes of HBM traffic per
+ * sample while K <= P.
+ * The K frames of a vector are cut into nseg = ceil(K / 32) segments of P = ceil(K / nseg) frames
+ * (nsh_psd_segment; a plan constant that depends on K alone: K up to 32, 17 at K = 33, 32 at 1024; the
+ * last segment may be shorter); a segment's frames are added in order in fp32 registers. With one segment the result is
+ * stored at once (one launch of nsh_psd_kernel). With more, the segments' sums go to scratch memory
+ * the plan owns and a second small kernel adds each vector's segments in a fixed order; a call with
+ * more segments than the scratch holds runs in batches of whole vectors. Because of the scratch a
+ * plan serves one stream at a time.
+ * Cut invariance: the chain of additions of a vector depends on (N, K, P) alone, so a vector's N
+ * outputs are bit-identical whatever the number of vectors in the call, the vector's place in it,
+ * the grid cap and the vector's slot in a wave or workgroup (nsh_psd_tile segments share a workgroup
+ * step). No float atomics.
+ * Non-finite samples: a non-finite sample makes the N outputs of its own vector non-finite and leaves
+ * every other vector bit-identical; the same holds for a frame whose |X|^2 overflows fp32.
+ * Accuracy: with X_f the float64 transform, d_f = 1e-5 max_k |X_f[k]| and g = (K + 2) 2^-24,
+ *   |out_j[k] - P_j[k]| <= scale * [sum_f (2 |X_f[k]| d_f + d_f^2) + g sum_f |X_f[k]|^2]
+ * Refused before any HIP call, in this order. nsh_psd_plan_create: a NULL plan out-pointer; an
+ * fft_size that is not a power of two in [16, 8192]; navg outside [1, 65536]; a non-finite window
+ * entry; a scale that is not finite or not > 0. nsh_psd_cf: nvec <= 0 returns 0 and launches
+ * nothing, whatever the other arguments; then a NULL in or out; in == out; a NULL plan; nvec so large
+ * that the byte counts overflow. nsh_psd_grid_cap: a negative cap, then a NULL plan; it bounds the
+ * workgroups of the grid-stride walk over the segments (0 restores the default) and the output does
+ * not depend on it. An armed nsh_time_next_launch pair is taken by the call: its start is recorded
+ * with the first launch and its stop with the last (dropped when nothing is launched). Runs on the
+ * current device, which must be the plan's.
+ * Measured: DESIGN.md section 4.9. */
+int nsh_psd_plan_create(int dev, int fft_size, int navg, const float* window_host /* NULL: none */, int shift,
+                        float scale, int db, void** plan);
+int nsh_psd_plan_destroy(void* plan);                 /* NULL: 0 */
+int nsh_psd_fft_size(void* plan);                     /* N; 0 for NULL */
+int nsh_psd_navg(void* plan);                         /* K; 0 for NULL */
+int nsh_psd_segment(void* plan);                      /* P; 0 for NULL */
+int nsh_psd_tile(void* plan);                         /* segments per workgroup step; 0 for NULL */
+const char* nsh_psd_kernel(void* plan);               /* e.g. "k_psd<4096, false>"; "" for NULL */
+int nsh_psd_grid_cap(void* plan, int max_workgroups); /* 0 restores the default */
+int nsh_psd_cf(void* plan, const float* in, float* out, int64_t nvec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_synthesizer_ccf.hpp>
+#include <gnuradio/blocklib/blocks/psd.hpp>
 #include <gnuradio/blocklib/blocks/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/multiply_const.hpp>
 #include <gnuradio/blocklib/blocks/rotator_cc.hpp>
@@ -605,6 +606,61 @@ work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::
     std::memmove(_ext.data(), _ext.data() + n, (L - 1) * sizeof(gr_complex)); // the last L-1 inputs
     _ext.resize(L - 1);
     out[0].n_produced = (int)n;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- psd_vcf: radix-2 in double, squares and sum in double, rounded once --------------------------
+psd_vcf::psd_vcf(size_t fft_size, size_t navg, const std::vector<float>& window, bool shift, float scale, bool db)
+    : decim_block("psd_vcf", (unsigned)navg), _fft_size(fft_size), _navg(navg), _shift(shift), _db(db), _scale(scale), _window(window)
+{
+    if (fft_size < 16 || fft_size > 8192 || (fft_size & (fft_size - 1)))
+        throw std::invalid_argument("psd_vcf: fft_size must be a power of two in [16, 8192]");
+    if (navg < 1 || navg > 65536) throw std::invalid_argument("psd_vcf: navg must be in [1, 65536]");
+    if (!window.empty() && window.size() != fft_size) throw std::invalid_argument("psd_vcf: the window must have fft_size entries");
+    for (float w : window)
+        if (!std::isfinite(w)) throw std::invalid_argument("psd_vcf: a window entry is not finite");
+    if (!std::isfinite(scale) || scale < 0.f) throw std::invalid_argument("psd_vcf: scale must be finite and > 0 (0: 1 / navg)");
+    if (scale == 0.f) _scale = 1.f / (float)navg;
+    _tw.resize(fft_size / 2);
+    for (size_t t = 0; t < fft_size / 2; ++t) {
+        const double a = -2.0 * M_PI * (double)t / (double)fft_size;
+        _tw[t] = { std::cos(a), std::sin(a) };
+    }
+    _a.resize(fft_size);
+    _sum.resize(fft_size);
+}
+
+work_return_code_t psd_vcf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const size_t N = _fft_size, H = N / 2;
+    const gr_complex* x = static_cast<const gr_complex*>(in[0].buffer->read_ptr());
+    float* y = static_cast<float*>(out[0].buffer->write_ptr());
+    size_t bits = 0;
+    while (((size_t)1 << bits) < N) ++bits;
+    for (int j = 0; j < out[0].n_items; ++j, y += N) {
+        std::fill(_sum.begin(), _sum.end(), 0.0);
+        for (size_t f = 0; f < _navg; ++f, x += N) {
+            for (size_t n = 0; n < N; ++n) {
+                const float w = _window.empty() ? 1.f : _window[n];
+                size_t rev = 0;
+                for (size_t b = 0; b < bits; ++b) rev |= ((n >> b) & 1) << (bits - 1 - b);
+                _a[rev] = { (double)(x[n].real() * w), (double)(x[n].imag() * w) };
+            }
+            for (size_t len = 2; len <= N; len <<= 1)
+                for (size_t i = 0; i < N; i += len)
+                    for (size_t k = 0; k < len / 2; ++k) {
+                        const std::complex<double> u = _a[i + k], v = _a[i + k + len / 2] * _tw[k * (N / len)];
+                        _a[i + k] = u + v;
+                        _a[i + k + len / 2] = u - v;
+                    }
+            for (size_t k = 0; k < N; ++k) _sum[k] += std::norm(_a[k]);
+        }
+        for (size_t k = 0; k < N; ++k) {
+            const double p = (double)_scale * _sum[_shift ? k ^ H : k];
+            y[k] = (float)(_db ? 10.0 * std::log10(p) : p);
+        }
+    }
+    out[0].n_produced = out[0].n_items;
     return work_return_code_t::WORK_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <gnuradio/blocklib/hip/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/pfb_channelizer_ccf.hpp>
 #include <gnuradio/blocklib/hip/pfb_synthesizer_ccf.hpp>
+#include <gnuradio/blocklib/hip/psd.hpp>
 #include <gnuradio/blocklib/hip/rational_resampler_ccf.hpp>
 #include <gnuradio/blocklib/hip/rotator_cc.hpp>
 #include <gnuradio/blocklib/hip/synth_source.hpp>
@@ -713,6 +714,62 @@ work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::
 }
 
 double fft_filter_ccc::kernel_ms() { return _ev.sum_ms(); }
+
+// ---- spectrum estimate: windowed FFT, |X|^2, sum over navg frames ---------------------------------
+psd_vcf::psd_vcf(size_t fft_size, size_t navg, const std::vector<float>& window, bool shift, float scale, bool db)
+    : decim_block("psd_vcf (hip)", (unsigned)navg), _fft_size(fft_size), _navg(navg), _shift(shift), _db(db), _scale(scale),
+      _window(window), _ev("hip::psd_vcf")
+{
+    // what nsh_psd_plan_create refuses, in its order
+    if (fft_size < 16 || fft_size > 8192 || (fft_size & (fft_size - 1)))
+        throw std::invalid_argument("hip::psd_vcf: fft_size must be a power of two in [16, 8192]");
+    if (navg < 1 || navg > 65536) throw std::invalid_argument("hip::psd_vcf: navg must be in [1, 65536]");
+    if (!window.empty() && window.size() != fft_size)
+        throw std::invalid_argument("hip::psd_vcf: the window must have fft_size entries");
+    for (float w : window)
+        if (!std::isfinite(w)) throw std::invalid_argument("hip::psd_vcf: a window entry is not finite");
+    if (!std::isfinite(scale) || scale < 0.f) throw std::invalid_argument("hip::psd_vcf: scale must be finite and > 0 (0: 1 / navg)");
+    if (scale == 0.f) _scale = 1.f / (float)navg;
+}
+psd_vcf::~psd_vcf() { nsh_psd_plan_destroy(_plan); }
+
+std::string psd_vcf::kernel() const { return _plan ? nsh_psd_kernel(_plan) : std::string(); }
+
+bool psd_vcf::start()
+{
+    const int dev = current_device();
+    if (_plan && _plan_dev != dev) {
+        _ev.release(); // the events belong to the old device too
+        nsh_psd_plan_destroy(_plan);
+        _plan = nullptr;
+    }
+    if (!_plan) {
+        check(nsh_psd_plan_create(dev, (int)_fft_size, (int)_navg, _window.empty() ? nullptr : _window.data(), _shift ? 1 : 0, _scale,
+                                  _db ? 1 : 0, &_plan),
+              "hip::psd_vcf plan");
+        _plan_dev = dev;
+    }
+    _ev.reuse();
+    _timed_vectors = 0;
+    return block::start();
+}
+
+work_return_code_t psd_vcf::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n = out[0].n_items; // decim_block::do_work: in[0].n_items == navg * n
+    void* s = current_stream();
+    if (_timing) _ev.arm(s);
+    check(nsh_psd_cf(_plan, (const float*)in[0].buffer->read_ptr(), (float*)out[0].buffer->write_ptr(), n, s), "hip::psd_vcf");
+    if (_timing) {
+        _ev.recorded(s);
+        _timed_vectors += (uint64_t)n;
+    }
+    ++_launches;
+    out[0].n_produced = n;
+    return work_return_code_t::WORK_OK;
+}
+
+double psd_vcf::kernel_ms() { return _ev.sum_ms(); }
 
 // ---- synthetic source ----------------------------------------------------------------
 work_return_code_t synth_source::work(std::vector<block_work_input>&, std::vector<block_work_output>& out)

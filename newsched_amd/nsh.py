@@ -129,6 +129,15 @@ SIGNATURES = {
     "nsh_fft_filter_kernel": (C.c_char_p, [_vp]),
     "nsh_fft_filter_grid_cap": (_i, [_vp, _i]),
     "nsh_fft_filter_ccc": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_psd_plan_create": (_i, [_i, _i, _i, C.POINTER(_f), _i, _f, _i, C.POINTER(_vp)]),
+    "nsh_psd_plan_destroy": (_i, [_vp]),
+    "nsh_psd_fft_size": (_i, [_vp]),
+    "nsh_psd_navg": (_i, [_vp]),
+    "nsh_psd_segment": (_i, [_vp]),
+    "nsh_psd_tile": (_i, [_vp]),
+    "nsh_psd_kernel": (C.c_char_p, [_vp]),
+    "nsh_psd_grid_cap": (_i, [_vp, _i]),
+    "nsh_psd_cf": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -342,6 +351,42 @@ class FftFilterPlan(_Plan):
         """n outputs from n inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw samples."""
         check(lib().nsh_fft_filter_ccc(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n,
                                        stream_ptr(stream)), "nsh_fft_filter_ccc")
+
+
+class PsdPlan(_Plan):
+    """Spectrum estimate: windowed forward FFT of fft_size points, |X|^2, summed over navg frames and
+    scaled (scale None: 1 / navg), optionally shifted and as 10 log10; see nsh_psd_cf. One stream at
+    a time: a plan with navg > segment owns scratch memory."""
+
+    _destroy = "nsh_psd_plan_destroy"
+
+    def __init__(self, fft_size: int, navg: int, window=None, shift: bool = False, scale=None, db: bool = False,
+                 device: int = 0):
+        self.fft_size = int(fft_size)
+        self.navg = int(navg)
+        self.shift = bool(shift)
+        self.db = bool(db)
+        self.scale = float(1.0 / max(self.navg, 1) if scale is None else scale)
+        arr = None
+        if window is not None:
+            w, arr = self._taps_arg(window)
+            if w.size != self.fft_size:
+                raise NshError(f"PsdPlan: the window has {w.size} entries, fft_size is {self.fft_size}")
+        h = C.c_void_p()
+        check(lib().nsh_psd_plan_create(device, self.fft_size, self.navg, arr, 1 if shift else 0, self.scale,
+                                        1 if db else 0, C.byref(h)), "nsh_psd_plan_create")
+        self._h = h
+        self.segment = lib().nsh_psd_segment(h)
+        self.tile = lib().nsh_psd_tile(h)
+        self.kernel = lib().nsh_psd_kernel(h).decode()
+
+    def grid_cap(self, max_workgroups: int = 0):
+        """At most max_workgroups workgroups per launch (0: the default); the output does not depend on it."""
+        check(lib().nsh_psd_grid_cap(self._h, int(max_workgroups)), "nsh_psd_grid_cap")
+
+    def __call__(self, x, y, nvec: int, stream=None):
+        """nvec vectors of fft_size floats from nvec * navg * fft_size complex samples."""
+        check(lib().nsh_psd_cf(self._h, ptr(x), ptr(y), nvec, stream_ptr(stream)), "nsh_psd_cf")
 
 
 class FirPlan(_Plan):
