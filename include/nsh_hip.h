@@ -522,6 +522,69 @@ int nsh_fft_filter_grid_cap(void* plan, int max_workgroups);
 int nsh_fft_filter_ccc(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n,
                        void* stream);
 
+/* ---- freq_xlating_fft_filter_ccc: tune, filter with complex taps and decimate by overlap-save
+ * (GNU Radio's freq_xlating_fft_filter_ccc) ----
+ * h = taps_host: ntaps = L complex fp32 taps as (re, im) pairs, 1 <= L <= 4096; D = decim in
+ * {1, 2, 4, 8, 16, 32, 64}; inc = nsh_phase_inc(-freq_norm); nsh_fir_xlat_ccf's definition with
+ * complex taps:
+ *   y[m] = sum_{k<L} h[k] * x[mD-k] * exp(+j 2 pi phase(first_index + mD - k))
+ *        = exp(+j 2 pi phase(first_index + mD)) * sum_{k<L} g[k] * x[mD-k]
+ *   phase(n) = ((n * inc) mod 2^64) / 2^64 turns,  g[k] = h[k] * exp(-j 2 pi ((k * inc) mod 2^64) / 2^64)
+ * The second line is what runs: the band-pass taps g are formed in double on the host from the
+ * 64-bit inc, Hs[k] = (1/N) DFT_N(g) is rounded once to fp32, and the remaining rotation is applied
+ * to the outputs at the phase ((first_index + m*D) * inc) mod 2^64 in uint64 wrap-around, so an
+ * output's phase does not depend on how the stream is cut into calls (its phasor is the rounded
+ * product of two: that of the first output its lane holds in the frame and that of the distance from
+ * it, each from the top 32 bits of its exact 64-bit phase). With inc == 0 the rotation is skipped,
+ * not multiplied by one. A call consumes n_out * D inputs. History as nsh_fir_xlat_ccf (L-1 raw samples,
+ * hist_out bit-exact, must not alias hist_in, required when L > 1).
+ * Frames: N = fft_size in {1024, 2048, 4096, 8192} with L <= N/2; 0 lets the plan choose by
+ * nsh_fft_filter_plan_create's rule. O = L-1 rounded up to a multiple of D (nsh_fft_xlat_overlap),
+ * V = N - O (nsh_fft_xlat_valid), Vd = V/D outputs per frame, M = N/D. Frame f of a call owns
+ * out[f*Vd, (f+1)*Vd) up to n_out and reads the window of inputs [fV-O, fV-O+N): positions in
+ * [-(L-1), 0) come from the history (or are zeros), positions below are zeros (they reach discarded
+ * outputs only), positions at or past n_out*D are zeros; nothing at or past out[n_out] is stored.
+ * One launch of k_fft_xlat<N, D> per call: window -> forward FFT of N -> times Hs -> fold
+ * Z[k'] = Y[k'] + Y[k'+M] + ... + Y[k'+(D-1)M] (in this order) -> unnormalised inverse FFT of M
+ * points -> drop the first O/D -> times the phasor -> store. nsh_fft_xlat_tile frames share a
+ * workgroup step.
+ * Rounding: as nsh_fft_filter_ccc, an output's rounding depends on where its frame starts, so two
+ * chained calls agree with one call to the bound below, not bit for bit; the phase and hist_out are
+ * exact. Within a call a frame's outputs depend on its window, first_index and its place in the
+ * call's frame grid alone, bit for bit, whatever follows it, the workgroup that runs it and the
+ * grid cap. D = 1 with freq_norm = 0 is bit-identical to nsh_fft_filter_ccc at the same fft_size.
+ * Accuracy: for output m in frame f, with y_ref the float64 evaluation of the first line,
+ *   |y - y_ref| <= 1e-5 |y_ref| + 1e-6 * max|x over frame f's window| * sum_k |h[k]|
+ * Non-finite samples: a non-finite sample makes non-finite every output of every frame whose window
+ * holds it, and touches no other frame.
+ * in, out and the histories need only 8-byte alignment.
+ * Refused before any HIP call, in this order. nsh_fft_xlat_plan_create: a NULL taps_host or plan
+ * out-pointer; ntaps outside [1, 4096]; a non-finite tap; a decim that is not a power of two in
+ * [1, 64] (nsh_fir_xlat_ccf stays the entry point for other decimations); a non-finite freq_norm; an
+ * fft_size that is neither 0 nor one of the four sizes; ntaps > fft_size / 2. nsh_fft_xlat_ccc:
+ * n_out <= 0 returns 0 and launches nothing, whatever the other arguments; then a NULL in or out;
+ * in == out; hist_out aliasing hist_in; a NULL plan; a missing hist_out when ntaps > 1; n_out * D
+ * too large for one call. nsh_fft_xlat_grid_cap: a negative cap, then a NULL plan; 0 restores the
+ * default, and the output does not depend on it. An armed nsh_time_next_launch pair is taken by the
+ * one launch (dropped when nothing is launched). Runs on the current device, which must be the
+ * plan's. On a machine with no device at all nsh_fft_xlat_plan_create still makes the plan, so that its
+ * geometry can be asked for; its tables stay on the host, and the first nsh_fft_xlat_ccc (which needs
+ * a device) would upload them. Measured: DESIGN.md section 4.10. */
+int nsh_fft_xlat_plan_create(int dev, const float* taps_host /* ntaps (re, im) pairs */, int ntaps, int decim,
+                             double freq_norm, int fft_size /* 0: chosen by the plan */, void** plan);
+int nsh_fft_xlat_plan_destroy(void* plan);            /* NULL: 0 */
+int nsh_fft_xlat_fft_size(void* plan);                /* N; 0 for NULL */
+int nsh_fft_xlat_decim(void* plan);                   /* D; 0 for NULL */
+int nsh_fft_xlat_overlap(void* plan);                 /* O; 0 for NULL */
+int nsh_fft_xlat_valid(void* plan);                   /* V = N - O; 0 for NULL */
+int nsh_fft_xlat_history(void* plan);                 /* ntaps - 1; 0 for NULL */
+int nsh_fft_xlat_phase_inc(void* plan, uint64_t* inc); /* NULL plan or inc: refused */
+int nsh_fft_xlat_tile(void* plan);                    /* frames per workgroup step; 0 for NULL */
+const char* nsh_fft_xlat_kernel(void* plan);          /* e.g. "k_fft_xlat<2048, 8>"; "" for NULL */
+int nsh_fft_xlat_grid_cap(void* plan, int max_workgroups);
+int nsh_fft_xlat_ccc(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n_out,
+                     uint64_t first_index, void* stream);
+
 /* ---- psd_vcf: windowed FFT, |X|^2 and the sum over K frames (fft_vcc -> complex_to_mag_squared ->
  * integrate_ff -> nlog10_ff) in one pass over the input ----
  * N = fft_size, a power of two in [16, 8192]; K = navg in [1, 65536]; w = window_host, N floats

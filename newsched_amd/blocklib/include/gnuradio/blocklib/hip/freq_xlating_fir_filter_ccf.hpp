@@ -11,6 +11,14 @@
 // 16 (0.83x); at D = 1, 2 and 4 the staged pair is faster (2.5x, 1.6x, 1.5x), because there the MFMA
 // FIR does the arithmetic this kernel does on the vector ALUs. At D = 16 with 255 taps the two are
 // level (1.04x), and the staged pair is limited to decimation 1, 2, 4, 8 and 16.
+//
+// When to prefer hip::freq_xlating_fft_filter_ccf instead (the same 127 taps
+// and 2^26 inputs, kernel times of one run): at every power-of-two decimation up to 16 the
+// overlap-save block is faster than this one, 229 / 257 / 220 / 208 / 205 us at D = 1 / 2 / 4 / 8 / 16
+// against 809 / 454 / 406 / 251 / 221 us here, and than the staged pair at each of them (355 / 312 /
+// 292 / 309 / 286 us); at (D, taps) = (16, 255) it takes 236 us against 283 here. This block stays
+// the faster one at D = 64 (164 us against 204 at 127 taps; level, 286 against 295, at 1024 taps) and
+// the only one for a decimation that is no power of two.
 #pragma once
 #include <gnuradio/blocklib/hip/fir_stream_state.hpp>
 #include <gnuradio/decim_block.hpp>

@@ -3,6 +3,7 @@
 #include <gnuradio/blocklib/blocks/fft.hpp>
 #include <gnuradio/blocklib/blocks/fft_filter.hpp>
 #include <gnuradio/blocklib/blocks/fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/blocks/freq_xlating_fft_filter_ccc.hpp>
 #include <gnuradio/blocklib/blocks/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_arb_resampler_ccf.hpp>
 #include <gnuradio/blocklib/blocks/pfb_channelizer_ccf.hpp>
@@ -606,6 +607,64 @@ work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::
     std::memmove(_ext.data(), _ext.data() + n, (L - 1) * sizeof(gr_complex)); // the last L-1 inputs
     _ext.resize(L - 1);
     out[0].n_produced = (int)n;
+    return work_return_code_t::WORK_OK;
+}
+
+// ---- freq_xlating_fft_filter_ccc: the direct form in double, the 64-bit phase ----------------------
+freq_xlating_fft_filter_ccc::freq_xlating_fft_filter_ccc(int decim, const std::vector<gr_complex>& taps, double center_freq,
+                                                         double samp_rate)
+    : decim_block("freq_xlating_fft_filter_ccc", (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim)
+{
+    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("freq_xlating_fft_filter_ccc: 1 to 4096 taps");
+    for (auto& t : taps)
+        if (!std::isfinite(t.real()) || !std::isfinite(t.imag()))
+            throw std::invalid_argument("freq_xlating_fft_filter_ccc: a tap is not finite");
+    if (decim < 1 || decim > 64 || (decim & (decim - 1)))
+        throw std::invalid_argument("freq_xlating_fft_filter_ccc: decimation must be a power of two in [1, 64]");
+    if (!(samp_rate > 0)) throw std::invalid_argument("freq_xlating_fft_filter_ccc: samp_rate must be positive");
+    if (!std::isfinite(center_freq / samp_rate))
+        throw std::invalid_argument("freq_xlating_fft_filter_ccc: the frequency must be finite");
+    _inc = phase_inc_turns(-(center_freq / samp_rate));
+}
+
+bool freq_xlating_fft_filter_ccc::start()
+{
+    _ext.assign(_taps.size() - 1, gr_complex(0, 0)); // zero history at stream start
+    _index = _first;
+    return block::start();
+}
+
+work_return_code_t freq_xlating_fft_filter_ccc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
+    const int L = (int)_taps.size();
+    const size_t n_in = (size_t)n_out * _decim;
+    gr_complex* y = static_cast<gr_complex*>(out[0].buffer->write_ptr());
+    if (_ext.size() < (size_t)(L - 1)) _ext.assign(L - 1, gr_complex(0, 0)); // not started: zeros
+    _ext.resize((size_t)(L - 1) + n_in);
+    std::memcpy(_ext.data() + (L - 1), in[0].buffer->read_ptr(), n_in * sizeof(gr_complex));
+    // rotate every sample of the window once (the raw history is rotated again with its own phase)
+    std::vector<std::complex<double>> rot(_ext.size());
+    for (size_t i = 0; i < _ext.size(); ++i) {
+        double s, c;
+        phase_sincos((_index + (uint64_t)i - (uint64_t)(L - 1)) * _inc, s, c);
+        const double re = _ext[i].real(), im = _ext[i].imag();
+        rot[i] = std::complex<double>(re * c - im * s, re * s + im * c);
+    }
+    for (int m = 0; m < n_out; ++m) {
+        const std::complex<double>* w = rot.data() + (size_t)m * _decim + (L - 1);
+        double re = 0, im = 0;
+        for (int k = 0; k < L; ++k) {
+            const double hr = _taps[k].real(), hi = _taps[k].imag(), xr = w[-k].real(), xi = w[-k].imag();
+            re += hr * xr - hi * xi;
+            im += hr * xi + hi * xr;
+        }
+        y[m] = gr_complex((float)re, (float)im);
+    }
+    std::memmove(_ext.data(), _ext.data() + n_in, (size_t)(L - 1) * sizeof(gr_complex)); // the last L-1 raw inputs
+    _ext.resize((size_t)(L - 1));
+    _index += (uint64_t)n_in;
+    out[0].n_produced = n_out;
     return work_return_code_t::WORK_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <gnuradio/blocklib/hip/fft_filter.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_cascade_ccf.hpp>
 #include <gnuradio/blocklib/hip/fir_filter_ccf.hpp>
+#include <gnuradio/blocklib/hip/freq_xlating_fft_filter_ccc.hpp>
 #include <gnuradio/blocklib/hip/freq_xlating_fir_filter_ccf.hpp>
 #include <gnuradio/blocklib/hip/multiply_const.hpp>
 #include <gnuradio/blocklib/hip/pfb_arb_resampler_ccf.hpp>
@@ -714,6 +715,71 @@ work_return_code_t fft_filter_ccc::work(std::vector<block_work_input>& in, std::
 }
 
 double fft_filter_ccc::kernel_ms() { return _ev.sum_ms(); }
+
+// ---- tune, overlap-save FIR with complex taps, decimate ---------------------------------------------
+freq_xlating_fft_filter_ccc::freq_xlating_fft_filter_ccc(int decim, const std::vector<gr_complex>& taps, double center_freq,
+                                                         double samp_rate, size_t fft_size, const char* name)
+    : decim_block(name, (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim), _fft_size(fft_size),
+      _state("hip::freq_xlating_fft_filter_ccc", nsh_fft_xlat_plan_destroy)
+{
+    // what nsh_fft_xlat_plan_create refuses, in its order
+    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: 1 to 4096 taps");
+    for (auto& t : taps)
+        if (!std::isfinite(t.real()) || !std::isfinite(t.imag()))
+            throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: a tap is not finite");
+    if (decim < 1 || decim > 64 || (decim & (decim - 1)))
+        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: decimation must be a power of two in [1, 64]");
+    if (!(samp_rate > 0)) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: samp_rate must be positive");
+    _freq_norm = center_freq / samp_rate;
+    if (!std::isfinite(_freq_norm)) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: the frequency must be finite");
+    if (fft_size != 0 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096 && fft_size != 8192)
+        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: fft_size must be 0, 1024, 2048, 4096 or 8192");
+    if (fft_size && taps.size() > fft_size / 2)
+        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: at most fft_size / 2 taps");
+}
+
+freq_xlating_fft_filter_ccc::~freq_xlating_fft_filter_ccc() = default;
+
+size_t freq_xlating_fft_filter_ccc::fft_size() const
+{
+    return _state.plan() ? (size_t)nsh_fft_xlat_fft_size(_state.plan()) : _fft_size;
+}
+uint64_t freq_xlating_fft_filter_ccc::phase_inc() const
+{
+    uint64_t inc = 0;
+    if (_state.plan()) nsh_fft_xlat_phase_inc(_state.plan(), &inc);
+    return inc;
+}
+std::string freq_xlating_fft_filter_ccc::kernel() const
+{
+    return _state.plan() ? nsh_fft_xlat_kernel(_state.plan()) : std::string();
+}
+
+bool freq_xlating_fft_filter_ccc::start()
+{
+    _state.prepare(current_device(), [this](int d, void** plan) {
+        check(nsh_fft_xlat_plan_create(d, reinterpret_cast<const float*>(_taps.data()), (int)_taps.size(), _decim, _freq_norm,
+                                       (int)_fft_size, plan),
+              "hip::freq_xlating_fft_filter_ccc plan");
+        return _taps.size() - 1;
+    });
+    _state.begin_run(current_stream());
+    _index = _first;
+    return block::start();
+}
+
+work_return_code_t freq_xlating_fft_filter_ccc::work(std::vector<block_work_input>& in, std::vector<block_work_output>& out)
+{
+    const int n_out = out[0].n_items; // decim_block::do_work: in[0].n_items == D * n_out
+    check(nsh_fft_xlat_ccc(_state.plan(), (const float*)in[0].buffer->read_ptr(), _state.hist_in(), _state.hist_out(),
+                           (float*)out[0].buffer->write_ptr(), n_out, _index, current_stream()),
+          "hip::freq_xlating_fft_filter_ccc");
+    _state.flip();
+    _index += (uint64_t)n_out * (uint64_t)_decim;
+    ++_launches;
+    out[0].n_produced = n_out;
+    return work_return_code_t::WORK_OK;
+}
 
 // ---- spectrum estimate: windowed FFT, |X|^2, sum over navg frames ---------------------------------
 psd_vcf::psd_vcf(size_t fft_size, size_t navg, const std::vector<float>& window, bool shift, float scale, bool db)

@@ -22,7 +22,7 @@
 // positions below 0 (V - H >= 2); the team that owns it loads it before the loop, history and input
 // through one resource each. Stores go through a resource over the frame's V outputs, clipped at
 // out + n; the lanes below H get an offset no resource reaches.
-#include "nsh_fft_team.hpp"
+#include "nsh_fft_ols.hpp"
 #include "nsh_stream_tile.hpp"
 
 #include <cmath>
@@ -38,23 +38,12 @@ using nsh::fft::fft_team;
 using nsh::fft::geom;
 using nsh::fft::pad;
 using nsh::fft::team_sync;
-
-// items samples (8 B each) from base on; built from wave-uniform values only (chunk_rsrc)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t span_rsrc(const float2* base, int64_t items)
-{
-    const uint64_t a = (uint64_t)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const int bytes = __builtin_amdgcn_readfirstlane((int)(items * 8));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, bytes, 0x00020000);
-}
-// a byte offset past every resource of this kernel (at most 64 KiB), far from wrapping
-constexpr int kNowhere = 0x40000000;
-
-__device__ __forceinline__ cf buf_load_cf(__amdgpu_buffer_rsrc_t r, int byte_off)
-{
-    return __builtin_bit_cast(cf, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, nsh::AUX_LD));
-}
+using nsh::ols::buf_load_cf;
+using nsh::ols::default_cap;
+using nsh::ols::default_fft_size;
+using nsh::ols::kNowhere;
+using nsh::ols::span_rsrc;
+using nsh::ols::spectrum_of;
 
 template <int N>
 constexpr bool hs_in_regs = geom<N>::NT <= 256;
@@ -180,53 +169,6 @@ void setup(filter_plan* p, const std::vector<float2>& spectrum, std::vector<floa
     for (int m = 0; m < 16; ++m)
         for (int t = 0; t < G::TT; ++t) ordered[m * G::TT + t] = spectrum[G::out_idx(t, m)];
 }
-
-// (1/N) DFT_N of the zero-padded taps, in double, rounded once (1/N is a power of two: exact)
-std::vector<float2> spectrum_of(const float* taps, int L, int N)
-{
-    std::vector<double> wr(N), wi(N);
-    for (int j = 0; j < N; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)N;
-        wr[j] = std::cos(a);
-        wi[j] = std::sin(a);
-    }
-    std::vector<float2> s(N);
-    for (int k = 0; k < N; ++k) {
-        double re = 0.0, im = 0.0;
-        for (int i = 0; i < L; ++i) {
-            const double hr = taps[2 * i], hi = taps[2 * i + 1];
-            if (hr == 0.0 && hi == 0.0) continue;
-            const int e = (int)(((int64_t)k * i) & (N - 1));
-            re += hr * wr[e] - hi * wi[e];
-            im += hr * wi[e] + hi * wr[e];
-        }
-        s[k] = make_float2((float)(re / N), (float)(im / N));
-    }
-    return s;
-}
-
-// Default frame size: the smallest N >= 4 pow2ceil(L) up to 4096, the smallest N >= 2 pow2ceil(L)
-// beyond, at least 1024: 1024 to 256 taps, 2048 to 512, 4096 to 2048, 8192 above. The candidates
-// were rule2 (N >= 2 pow2ceil(L)) and rule4 (N >= 4 pow2ceil(L)): fewer, longer frames overlap less,
-// and a frame of 8192 costs 1.5 times one of 4096 per sample (512 lanes, one workgroup per CU, the
-// spectrum re-read). Kernel times on 2^26 samples, rule2 / rule4 (tools/fft_filter_bench.py,
-// profiles/fft_filter_bench.json): 512 taps 345 / 345 us, 1024 taps 462 / 340 us,
-// 2048 taps 457 / 546 us; to 256 and above 2048 taps the two rules give the same size.
-int default_fft_size(int L)
-{
-    int p = 1;
-    while (p < L) p *= 2;
-    const int n = 4 * p <= 4096 ? 4 * p : 2 * p;
-    return n < 1024 ? 1024 : n;
-}
-
-// Workgroups of the grid-stride walk. A workgroup stages its size's twiddle tables once and
-// prefetches from its second step on; 127 taps on 2^26 samples under caps of 256 .. 16384
-// (tools/fft_filter_bench.py --cap-sweep), us at 256 / 512 / 1024 / 2048 / 8192
-// workgroups: N = 1024: 266 / 222 / 220 / 217 / 244, 2048: 341 / 255 / 254 / 253 / 273,
-// 4096: 315 / 253 / 251 / 254 / 270, 8192: 385 / 387 / 392 / 401 / 479. 512 to 2048 are level up to
-// 4096 points (within the rounds' spread), 256 and 512 at 8192.
-constexpr int default_cap(int n) { return n <= 4096 ? 1024 : 512; }
 
 } // namespace
 

@@ -1,5 +1,5 @@
-// The team transform of the plan-based FFT kernels: k_fft<N> (nsh_fft_plan.hip) and k_fft_filter<N>
-// (nsh_fft_filter.hip). nsh_fft_plan.hip's header comment has the organisation (Stockham autosort,
+// The team transform of the plan-based FFT kernels: k_fft<N> (nsh_fft_plan.hip), k_fft_filter<N>
+// (nsh_fft_filter.hip) and k_fft_xlat<N, D> (nsh_fft_xlat.hip). nsh_fft_plan.hip's header comment has the organisation (Stockham autosort,
 // 16 samples per lane, teams of TT lanes, radix plan, per-pass twiddle tables); this file holds its
 // geometry, the passes, fft_team and the host's table builder. gfx950 only.
 #pragma once
@@ -75,8 +75,9 @@ __device__ __forceinline__ void dft_r(cf (&a)[R])
     }
 }
 
-// pass (Ns, R) of the team: image -> twiddles -> butterflies -> v[i + NB r]
-template <int N, int Ns, int R, bool INV>
+// pass (Ns, R) of the team: image -> twiddles -> butterflies -> v[i + NB r]. TWK > 1: tw is the
+// pass's table of a larger size whose radix here is TWK R (W_{Ns R}^{kr} = W_{Ns TWK R}^{k TWK r}).
+template <int N, int Ns, int R, bool INV, int TWK = 1>
 __device__ __forceinline__ void pass_read(cf (&v)[16], const cf* __restrict__ img, const cf* __restrict__ tw, int t)
 {
     constexpr int NB = 16 / R, Q = N / R, TT = geom<N>::TT;
@@ -87,7 +88,7 @@ __device__ __forceinline__ void pass_read(cf (&v)[16], const cf* __restrict__ im
 #pragma unroll
         for (int r = 0; r < R; ++r) a[r] = img[pad(base + Q * r)];
 #pragma unroll
-        for (int r = 1; r < R; ++r) a[r] = cmulw(a[r], conj_if<INV>(tw[(r - 1) * Ns + k]));
+        for (int r = 1; r < R; ++r) a[r] = cmulw(a[r], conj_if<INV>(tw[(r * TWK - 1) * Ns + k]));
         dft_r<R, INV>(a);
 #pragma unroll
         for (int r = 0; r < R; ++r) v[i + NB * r] = a[r];
@@ -107,31 +108,32 @@ __device__ __forceinline__ void pass_write(const cf (&v)[16], cf* __restrict__ i
 }
 
 // the passes from sub-transform size Ns on; the image holds pass input. The last pass's output
-// stays in v (geom::out_idx).
-template <int N, int Ns, bool INV>
+// stays in v (geom::out_idx). tw holds the tables of size NTAB >= N (pass_tables(NTAB)): a pass's
+// table depends on (Ns, R) alone, so a smaller transform walks a prefix of a larger one's.
+template <int N, int Ns, bool INV, int NTAB = N>
 __device__ __forceinline__ void passes_from(cf (&v)[16], cf* __restrict__ img, const cf* __restrict__ tw, int t)
 {
     constexpr int R = radix_at(N, Ns);
     constexpr bool WG = geom<N>::WG;
-    pass_read<N, Ns, R, INV>(v, img, tw, t);
+    pass_read<N, Ns, R, INV, radix_at(NTAB, Ns) / R>(v, img, tw, t);
     team_sync<WG>(); // all reads done before the image is rewritten (by the next pass or the next tile)
     if constexpr (Ns * R < N) {
         pass_write<N, Ns, R>(v, img, t);
         team_sync<WG>();
-        passes_from<N, Ns * R, INV>(v, img, tw + (R - 1) * Ns, t);
+        passes_from<N, Ns * R, INV, NTAB>(v, img, tw + (R - 1) * Ns, t);
     }
 }
 
 // Transform of the team's frames held as v[r] = x[geom::in_idx(t, r)]; on return v[m] =
 // X[geom::out_idx(t, m)].
-template <int N, bool INV>
+template <int N, bool INV, int NTAB = N>
 __device__ __forceinline__ void fft_team(cf (&v)[16], cf* __restrict__ img, const cf* __restrict__ tw, int t)
 {
     dft16<INV>(v);
     if constexpr (N > 16) {
         pass_write<N, 1, 16>(v, img, t);
         team_sync<geom<N>::WG>();
-        passes_from<N, 16, INV>(v, img, tw, t);
+        passes_from<N, 16, INV, NTAB>(v, img, tw, t);
     }
 }
 

@@ -33,6 +33,7 @@
 //                   Instantiations by decimation, T D <= 8192 samples (two workgroups per CU on
 //                   160 KiB when 2^a >= 8): D <= 4 <8,1>, <= 8 <4,1>, <= 16 <4,2>, <= 32 <4,4>,
 //                   <= 64 <2,4>.
+#include "nsh_phase.hpp"
 #include "nsh_stream_tile.hpp"
 
 #include <algorithm>
@@ -49,21 +50,9 @@ constexpr int kStage = 8; // sample pairs a lane loads before it rotates the fir
 
 using nsh::fma2;
 using nsh::nf4;
+using nsh::crot;
+using nsh::phasor;
 using nsh::virt;
-
-// exp(j 2 pi p / 2^64) from the top 32 bits of p
-__device__ __forceinline__ float2 phasor(uint64_t p)
-{
-    const int s = (int)(uint32_t)(p >> 32);
-    float sn, cs;
-    sincospif((float)s * 4.656612873077392578125e-10f /* 2^-31 */, &sn, &cs);
-    return make_float2(cs, sn);
-}
-// a * w, complex; one rounded product and one FMA per component
-__device__ __forceinline__ float2 crot(float2 a, float2 w)
-{
-    return make_float2(__builtin_fmaf(-a.y, w.y, a.x * w.x), __builtin_fmaf(a.x, w.y, a.y * w.x));
-}
 
 __device__ __forceinline__ void rotate_one(const float2* in, float2* out, int64_t i, uint64_t inc, uint64_t first)
 {

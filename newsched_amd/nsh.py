@@ -129,6 +129,18 @@ SIGNATURES = {
     "nsh_fft_filter_kernel": (C.c_char_p, [_vp]),
     "nsh_fft_filter_grid_cap": (_i, [_vp, _i]),
     "nsh_fft_filter_ccc": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nsh_fft_xlat_plan_create": (_i, [_i, C.POINTER(_f), _i, _i, C.c_double, _i, C.POINTER(_vp)]),
+    "nsh_fft_xlat_plan_destroy": (_i, [_vp]),
+    "nsh_fft_xlat_fft_size": (_i, [_vp]),
+    "nsh_fft_xlat_decim": (_i, [_vp]),
+    "nsh_fft_xlat_overlap": (_i, [_vp]),
+    "nsh_fft_xlat_valid": (_i, [_vp]),
+    "nsh_fft_xlat_history": (_i, [_vp]),
+    "nsh_fft_xlat_phase_inc": (_i, [_vp, C.POINTER(_u64)]),
+    "nsh_fft_xlat_tile": (_i, [_vp]),
+    "nsh_fft_xlat_kernel": (C.c_char_p, [_vp]),
+    "nsh_fft_xlat_grid_cap": (_i, [_vp, _i]),
+    "nsh_fft_xlat_ccc": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _u64, _vp]),
     "nsh_psd_plan_create": (_i, [_i, _i, _i, C.POINTER(_f), _i, _f, _i, C.POINTER(_vp)]),
     "nsh_psd_plan_destroy": (_i, [_vp]),
     "nsh_psd_fft_size": (_i, [_vp]),
@@ -351,6 +363,46 @@ class FftFilterPlan(_Plan):
         """n outputs from n inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw samples."""
         check(lib().nsh_fft_filter_ccc(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n,
                                        stream_ptr(stream)), "nsh_fft_filter_ccc")
+
+
+class FftXlatPlan(_Plan):
+    """Tune by freq_norm (cycles per input sample), filter with complex taps and decimate by
+    decim in {1, 2, ..., 64} by overlap-save in one launch (window -> FFT -> times the band-pass taps'
+    spectrum -> fold to fft_size / decim bins -> inverse FFT -> rotate -> valid part); see
+    nsh_fft_xlat_ccc. fft_size 0: chosen by the plan."""
+
+    _destroy = "nsh_fft_xlat_plan_destroy"
+
+    def __init__(self, taps, decim: int = 1, freq_norm: float = 0.0, fft_size: int = 0, device: int = 0):
+        import numpy as np
+
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.complex64))
+        self.ntaps = int(t.size)
+        h = C.c_void_p()
+        check(lib().nsh_fft_xlat_plan_create(device, t.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)),
+                                             self.ntaps, int(decim), float(freq_norm), int(fft_size), C.byref(h)),
+              "nsh_fft_xlat_plan_create")
+        self._h = h
+        self.fft_size = lib().nsh_fft_xlat_fft_size(h)
+        self.decim = lib().nsh_fft_xlat_decim(h)
+        self.overlap = lib().nsh_fft_xlat_overlap(h)
+        self.valid = lib().nsh_fft_xlat_valid(h)
+        self.hist_len = lib().nsh_fft_xlat_history(h)
+        self.tile = lib().nsh_fft_xlat_tile(h)
+        self.kernel = lib().nsh_fft_xlat_kernel(h).decode()
+        inc = C.c_uint64()
+        check(lib().nsh_fft_xlat_phase_inc(h, C.byref(inc)), "nsh_fft_xlat_phase_inc")
+        self.phase_inc = int(inc.value)
+
+    def grid_cap(self, max_workgroups: int = 0):
+        """At most max_workgroups workgroups per launch (0: the default); the output does not depend on it."""
+        check(lib().nsh_fft_xlat_grid_cap(self._h, int(max_workgroups)), "nsh_fft_xlat_grid_cap")
+
+    def __call__(self, x, hist_in, hist_out, y, n_out: int, first_index: int = 0, stream=None):
+        """n_out outputs from n_out * decim inputs; hist_in (or None = zeros) / hist_out: ntaps-1 raw
+        samples; first_index: the absolute stream index of x[0] (mod 2^64)."""
+        check(lib().nsh_fft_xlat_ccc(self._h, ptr(x), _opt_ptr(hist_in), _opt_ptr(hist_out), ptr(y), n_out,
+                                     first_index & 0xFFFFFFFFFFFFFFFF, stream_ptr(stream)), "nsh_fft_xlat_ccc")
 
 
 class PsdPlan(_Plan):
