@@ -487,7 +487,7 @@ int nsh_fft_c2c(void* plan, const float* in, float* out, int64_t nframes, void* 
  * V = N - (L-1) valid outputs per frame: frame f of a call owns out[fV, (f+1)V) up to n and reads
  * the window of inputs [fV-(L-1), fV-(L-1)+N); window positions below 0 come from the history (or
  * are zeros), positions at or past n are zeros, nothing at or past out[n] is stored. One launch of
- * k_fft_filter<N> per call: window -> forward FFT -> times Hs -> inverse FFT -> store of the valid
+ * k_fft_xlat<N, 1, false> per call: window -> forward FFT -> times Hs -> inverse FFT -> store of the valid
  * part, with
  *   Hs[k] = (1/N) sum_{n<L} h[n] e^{-2 pi i kn/N}
  * computed in double on the host and rounded once to fp32 (the 1/N is a power of two: exact).
@@ -517,7 +517,7 @@ int nsh_fft_filter_fft_size(void* plan);              /* N; 0 for NULL */
 int nsh_fft_filter_valid(void* plan);                 /* V = N - (ntaps - 1); 0 for NULL */
 int nsh_fft_filter_history(void* plan);               /* ntaps - 1; 0 for NULL */
 int nsh_fft_filter_tile(void* plan);                  /* frames per workgroup step; 0 for NULL */
-const char* nsh_fft_filter_kernel(void* plan);        /* e.g. "k_fft_filter<2048>"; "" for NULL */
+const char* nsh_fft_filter_kernel(void* plan);        /* e.g. "k_fft_xlat<2048, 1, false>"; "" for NULL */
 int nsh_fft_filter_grid_cap(void* plan, int max_workgroups);
 int nsh_fft_filter_ccc(void* plan, const float* in, const float* hist_in, float* hist_out, float* out, int64_t n,
                        void* stream);
@@ -552,7 +552,8 @@ int nsh_fft_filter_ccc(void* plan, const float* in, const float* hist_in, float*
  * chained calls agree with one call to the bound below, not bit for bit; the phase and hist_out are
  * exact. Within a call a frame's outputs depend on its window, first_index and its place in the
  * call's frame grid alone, bit for bit, whatever follows it, the workgroup that runs it and the
- * grid cap. D = 1 with freq_norm = 0 is bit-identical to nsh_fft_filter_ccc at the same fft_size.
+ * grid cap. D = 1 with freq_norm = 0 is the same kernel as nsh_fft_filter_ccc at the same fft_size
+ * (which runs it with the rotation compiled out: the same bits).
  * Accuracy: for output m in frame f, with y_ref the float64 evaluation of the first line,
  *   |y - y_ref| <= 1e-5 |y_ref| + 1e-6 * max|x over frame f's window| * sum_k |h[k]|
  * Non-finite samples: a non-finite sample makes non-finite every output of every frame whose window

@@ -1,6 +1,6 @@
 // blocks::fft_filter_ccc: CPU statement of GNU Radio's fft_filter_ccc at decimation 1 (complex
 // stream, complex taps), y[n] = sum_k h[k] x[n-k], zero initial history. It defines the semantics
-// that hip::fft_filter_ccc (k_fft_filter<N>, overlap-save on the GPU) is tested against, and computes
+// that hip::fft_filter_ccc (k_fft_xlat<N, 1, false>, overlap-save on the GPU) is tested against, and computes
 // them in the plain direct form, accumulated in double and rounded once per output: no frames, so its
 // output does not depend on how the stream is cut into work() calls. A gr::sync_block.
 // For real taps on the GPU, prefer hip::fft_filter_ccf to hip::fir_filter_ccf from 162 taps on (where

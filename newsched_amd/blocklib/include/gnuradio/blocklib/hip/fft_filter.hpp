@@ -1,6 +1,6 @@
 // gr::hip::fft_filter_ccc -- FIR filter with complex taps (1 to 4096) at decimation 1 by overlap-save,
 // GNU Radio's fft_filter_ccc: y[n] = sum_k h[k] x[n-k], one kernel launch per work()
-// (nsh_fft_filter_ccc, k_fft_filter<N>: window -> FFT -> times the taps' spectrum -> inverse FFT ->
+// (nsh_fft_filter_ccc, k_fft_xlat<N, 1, false>: window -> FFT -> times the taps' spectrum -> inverse FFT ->
 // valid part; about 16 B of HBM traffic per output whatever the tap count). gr::hip::fft_filter_ccf
 // is the same block for real taps (zero imaginary parts). fft_size is 1024, 2048, 4096 or 8192 with
 // ntaps <= fft_size / 2, or 0: 1024 up to 256 taps, 2048 up to 512, 4096 up to 2048, 8192 above.

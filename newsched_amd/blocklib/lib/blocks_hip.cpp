@@ -661,19 +661,25 @@ work_return_code_t channelizer_vcc::work(std::vector<block_work_input>& in, std:
 }
 
 // ---- overlap-save FIR with complex taps ---------------------------------------------------
+// What the overlap-save plans (nsh_fft_filter_plan_create, nsh_fft_xlat_plan_create) refuse, in
+// their order; between: what a plan checks after the taps and before the frame size.
+template <class F>
+static void check_ols_args(const std::string& name, const std::vector<gr_complex>& taps, size_t fft_size, F between)
+{
+    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument(name + ": 1 to 4096 taps");
+    for (auto& t : taps)
+        if (!std::isfinite(t.real()) || !std::isfinite(t.imag())) throw std::invalid_argument(name + ": a tap is not finite");
+    between();
+    if (fft_size != 0 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096 && fft_size != 8192)
+        throw std::invalid_argument(name + ": fft_size must be 0, 1024, 2048, 4096 or 8192");
+    if (fft_size && taps.size() > fft_size / 2) throw std::invalid_argument(name + ": at most fft_size / 2 taps");
+}
+
 fft_filter_ccc::fft_filter_ccc(const std::vector<gr_complex>& taps, size_t fft_size, const char* name)
     : sync_block(name), _taps(taps), _fft_size(fft_size), _state("hip::fft_filter_ccc", nsh_fft_filter_plan_destroy),
       _ev("hip::fft_filter_ccc")
 {
-    // what nsh_fft_filter_plan_create refuses, in its order
-    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("hip::fft_filter_ccc: 1 to 4096 taps");
-    for (auto& t : taps)
-        if (!std::isfinite(t.real()) || !std::isfinite(t.imag()))
-            throw std::invalid_argument("hip::fft_filter_ccc: a tap is not finite");
-    if (fft_size != 0 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096 && fft_size != 8192)
-        throw std::invalid_argument("hip::fft_filter_ccc: fft_size must be 0, 1024, 2048, 4096 or 8192");
-    if (fft_size && taps.size() > fft_size / 2)
-        throw std::invalid_argument("hip::fft_filter_ccc: at most fft_size / 2 taps");
+    check_ols_args("hip::fft_filter_ccc", taps, fft_size, [] {});
 }
 
 fft_filter_ccc::~fft_filter_ccc() = default;
@@ -722,20 +728,14 @@ freq_xlating_fft_filter_ccc::freq_xlating_fft_filter_ccc(int decim, const std::v
     : decim_block(name, (unsigned)(decim > 0 ? decim : 1)), _taps(taps), _decim(decim), _fft_size(fft_size),
       _state("hip::freq_xlating_fft_filter_ccc", nsh_fft_xlat_plan_destroy)
 {
-    // what nsh_fft_xlat_plan_create refuses, in its order
-    if (taps.empty() || taps.size() > 4096) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: 1 to 4096 taps");
-    for (auto& t : taps)
-        if (!std::isfinite(t.real()) || !std::isfinite(t.imag()))
-            throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: a tap is not finite");
-    if (decim < 1 || decim > 64 || (decim & (decim - 1)))
-        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: decimation must be a power of two in [1, 64]");
-    if (!(samp_rate > 0)) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: samp_rate must be positive");
-    _freq_norm = center_freq / samp_rate;
-    if (!std::isfinite(_freq_norm)) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: the frequency must be finite");
-    if (fft_size != 0 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096 && fft_size != 8192)
-        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: fft_size must be 0, 1024, 2048, 4096 or 8192");
-    if (fft_size && taps.size() > fft_size / 2)
-        throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: at most fft_size / 2 taps");
+    check_ols_args("hip::freq_xlating_fft_filter_ccc", taps, fft_size, [&] {
+        if (decim < 1 || decim > 64 || (decim & (decim - 1)))
+            throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: decimation must be a power of two in [1, 64]");
+        if (!(samp_rate > 0)) throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: samp_rate must be positive");
+        _freq_norm = center_freq / samp_rate;
+        if (!std::isfinite(_freq_norm))
+            throw std::invalid_argument("hip::freq_xlating_fft_filter_ccc: the frequency must be finite");
+    });
 }
 
 freq_xlating_fft_filter_ccc::~freq_xlating_fft_filter_ccc() = default;

@@ -1,6 +1,7 @@
-// What the overlap-save kernels share: k_fft_filter<N> (nsh_fft_filter.hip) and k_fft_xlat<N, D>
-// (nsh_fft_xlat.hip). Per-window buffer resources on the device; the taps' spectrum, the default
-// frame size and the default grid cap on the host. gfx950 only.
+// What the overlap-save kernel k_fft_xlat<N, D> (nsh_fft_xlat_kernel.hpp) and its plan
+// (nsh_fft_ols.hip) are built from. Per-window buffer resources on the device; the taps' spectrum,
+// the default frame size and the default grid cap on the host. gfx950 only.
+// The times below were measured on k_fft_filter<N>, which k_fft_xlat<N, 1, false> replaced (same sequence).
 #pragma once
 #include "nsh_fft_team.hpp"
 
@@ -57,7 +58,7 @@ std::vector<float2> spectrum_of(const T* taps, int L, int N)
 // beyond, at least 1024: 1024 to 256 taps, 2048 to 512, 4096 to 2048, 8192 above. The candidates
 // were rule2 (N >= 2 pow2ceil(L)) and rule4 (N >= 4 pow2ceil(L)): fewer, longer frames overlap less,
 // and a frame of 8192 costs 1.5 times one of 4096 per sample (512 lanes, one workgroup per CU, the
-// spectrum re-read). Kernel times of k_fft_filter on 2^26 samples, rule2 / rule4
+// spectrum re-read). Kernel times of fft_filter_ccc on 2^26 samples, rule2 / rule4
 // (tools/fft_filter_bench.py, profiles/fft_filter_bench.json): 512 taps 345 / 345 us,
 // 1024 taps 462 / 340 us, 2048 taps 457 / 546 us; to 256 and above 2048 taps the two rules give the
 // same size.
@@ -70,7 +71,7 @@ inline int default_fft_size(int L)
 }
 
 // Workgroups of the grid-stride walk. A workgroup stages its size's twiddle tables once and
-// prefetches from its second step on; k_fft_filter, 127 taps on 2^26 samples under caps of
+// prefetches from its second step on; fft_filter_ccc, 127 taps on 2^26 samples under caps of
 // 256 .. 16384 (tools/fft_filter_bench.py --cap-sweep), us at 256 / 512 / 1024 / 2048 /
 // 8192 workgroups: N = 1024: 266 / 222 / 220 / 217 / 244, 2048: 341 / 255 / 254 / 253 / 273,
 // 4096: 315 / 253 / 251 / 254 / 270, 8192: 385 / 387 / 392 / 401 / 479. 512 to 2048 are level up to

@@ -27,7 +27,7 @@
 // meets the same 16 window entries in every frame, so they are loaded once per kernel (1.0 without a
 // window: an exact multiply). The shift is index ^ N/2 on the store (forward) or the load (inverse).
 // N = 1024 without window and shift runs k_fft1024 (nsh_fft.hip).
-// The geometry, the passes and fft_team are in nsh_fft_team.hpp (k_fft_filter uses them too).
+// The geometry, the passes and fft_team are in nsh_fft_team.hpp (k_fft_xlat uses them too).
 #include "nsh_fft_team.hpp"
 
 #include <cstdlib>
@@ -43,6 +43,7 @@ using nsh::fft::geom;
 using nsh::fft::pad;
 using nsh::fft::pass_tables;
 using nsh::fft::team_sync;
+using nsh::fft::to_device;
 
 // LIN (N <= 1024): every global access is the wave's coalesced walk (sample t + 64 m), and the
 // registers of pass 1 and of the last pass are filled from / emptied into the image by a
@@ -198,15 +199,9 @@ int nsh_fft_plan_create(int dev, int fft_size, int inverse, const float* window_
                     (lin ? "true>" : "false>");
     if (!p->plain1024) {
         NSH_CK(hipSetDevice(dev));
-        const std::vector<float2> h = pass_tables(fft_size);
-        if (!h.empty()) {
-            NSH_CK(hipMalloc(&p->tw, h.size() * sizeof(float2)));
-            NSH_CK(hipMemcpy(p->tw, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-        }
-        if (window_host) {
-            NSH_CK(hipMalloc(&p->win, fft_size * sizeof(float)));
-            NSH_CK(hipMemcpy(p->win, window_host, fft_size * sizeof(float), hipMemcpyHostToDevice));
-        }
+        if (const int rc = to_device(pass_tables(fft_size), &p->tw)) return rc;
+        if (window_host)
+            if (const int rc = to_device(std::vector<float>(window_host, window_host + fft_size), &p->win)) return rc;
     }
     *plan = p.release();
     return 0;

@@ -1,5 +1,5 @@
 // The pieces every FFT kernel of libnsh_hip.so is built from (k_fft1024 and k_chan1024 in
-// nsh_fft.hip, k_fft<N> in nsh_fft_plan.hip, k_fft_filter<N> in nsh_fft_filter.hip; the last two
+// nsh_fft.hip, k_fft<N> in nsh_fft_plan.hip, k_fft_xlat<N, D> in nsh_fft_xlat_kernel.hpp; the last two
 // share the team transform of nsh_fft_team.hpp on top of this file): the register DFT16, the padded LDS image, the
 // conjugation switch, twiddle staging and the 16-samples-per-lane buffer loads and stores.
 // gfx950 only.
@@ -8,6 +8,7 @@
 #include "nsh_cplx.hpp"
 
 #include <cmath>
+#include <vector>
 
 namespace nsh {
 namespace fft {
@@ -108,6 +109,16 @@ struct lane64 {
     int j;
     __device__ __forceinline__ int operator()(int m) const { return j + 64 * m; }
 };
+
+// a plan's host table to a fresh allocation on the current device; nothing for an empty one
+template <typename T>
+int to_device(const std::vector<T>& h, T** dst)
+{
+    if (h.empty()) return 0;
+    NSH_CK(hipMalloc(dst, h.size() * sizeof(T)));
+    NSH_CK(hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
 
 // Workgroups of a grid-stride walk over groups of fw frames, at most cap
 inline unsigned frame_grid(int64_t nframes, int fw, int64_t cap)

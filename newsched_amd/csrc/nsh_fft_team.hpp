@@ -1,5 +1,5 @@
-// The team transform of the plan-based FFT kernels: k_fft<N> (nsh_fft_plan.hip), k_fft_filter<N>
-// (nsh_fft_filter.hip) and k_fft_xlat<N, D> (nsh_fft_xlat.hip). nsh_fft_plan.hip's header comment has the organisation (Stockham autosort,
+// The team transform of the plan-based FFT kernels: k_fft<N> (nsh_fft_plan.hip) and
+// k_fft_xlat<N, D> (nsh_fft_xlat_kernel.hpp). nsh_fft_plan.hip's header comment has the organisation (Stockham autosort,
 // 16 samples per lane, teams of TT lanes, radix plan, per-pass twiddle tables); this file holds its
 // geometry, the passes, fft_team and the host's table builder. gfx950 only.
 #pragma once

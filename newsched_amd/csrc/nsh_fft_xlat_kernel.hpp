@@ -1,15 +1,28 @@
-// k_fft_xlat<N, D>: the kernel of freq_xlating_fft_filter_ccc (nsh_fft_xlat.hip has the definition,
-// the frames and the entry points; nsh_fft_xlat_<N>.hip instantiate the seven D of one N each, so
-// that the 28 forms compile side by side). gfx950 only.
+// k_fft_xlat<N, D, ROT>: the kernel of freq_xlating_fft_filter_ccc (<N, D>) and of fft_filter_ccc
+// (<N, 1, false>: O = L-1, inc = 0, the rotation and its step table compiled out). nsh_fft_ols.hip
+// has the definitions, the frames and the entry points; nsh_fft_xlat_<N>.hip instantiate the forms
+// of one N each (seven D and the one without rotation), so that the 32 forms compile side by side.
+// gfx950 only.
 //
-// A team of geom<N>::TT = N/16 lanes holds one frame, as in k_fft_filter<N>, whose window loads
-// (one buffer resource per window, the next window's loads in flight across the arithmetic) and
-// register-resident Hs (N <= 4096) are carried over unchanged:
+// A team of geom<N>::TT = N/16 lanes (nsh_fft_team.hpp) holds one frame, 16 samples a lane:
 //
 //   window -> fft_team<N, false> -> times Hs -> image in natural order
 //          -> fold to M = N/D bins -> inverse of M points -> drop O/D -> times phasor -> store
 //
-// D = 1 has nothing to fold and runs k_fft_filter's own sequence (bit-identical to it at inc = 0).
+// D = 1 has nothing to fold: the lanes read the image back in in_idx order and run fft_team<N, true>.
+//
+// Hs lies in the order the lanes meet it after the forward transform (entry m TT + t is
+// Hs[geom::out_idx(t, m)]), so a wave reads it as whole lines. A lane meets the same 16 entries in
+// every frame: N <= 4096 keeps them in registers for the whole kernel, N = 8192 (512 lanes, 256
+// VGPRs each) reads them from L2 after every forward transform.
+//
+// Windows start at any 8-byte aligned sample and overlap, so a frame gets a buffer resource of its
+// own: base in + (fV-O), length what is left of the stream, at most N. What lies past the end reads
+// zeros without an address being formed for it, and the loop issues the same loads for every frame:
+// the next frame's stay in flight across this frame's arithmetic. Only frame 0 of a call has
+// positions below 0 (V >= O); the team that owns it loads it before the loop, history and input
+// through one resource each. Stores go through a resource over the frame's Vd outputs, clipped at
+// out + n_out; the lanes below O/D get an offset no resource reaches.
 //
 // Fold (D > 1). Z[k'] = ((Y[k'] + Y[k'+M]) + Y[k'+2M]) + ... + Y[k'+(D-1)M], d ascending, by all
 // lanes of the team: lane t sums bins k' = t + FL j, j < BPL = max(16/D, 1), over FL = M / BPL
@@ -33,12 +46,15 @@
 // takes one sincospif per frame, for its first output's phase, and multiplies it by
 // steps[m] = phasor(c(m) D inc) from a 16-entry LDS table for output m, which lies c(m) outputs on
 // (two phasors of 2^-32 turns of truncation each and one rounded complex product, in place of
-// sixteen sincospif a lane). inc == 0 skips the rotation (a uniform branch).
+// sixteen sincospif a lane). inc == 0 skips the rotation (a uniform branch); ROT = false has no
+// branch, no table and no phasor code: with them fft_filter_ccc's launches took 2 to 3 % longer at
+// N = 4096 and 8192 than the kernel without.
 //
-// Budgets, from the compiler's kernel-resource-usage remarks: LDS is k_fft_filter<N>'s (the twiddle
-// tables of N plus one padded image per team) and the 128-byte step table, 42.0 / 50.0 / 66.0 /
-// 132.0 KiB per workgroup at N = 1024 / 2048 / 4096 / 8192; 235 to 254 VGPRs, no AGPRs, two waves per
-// SIMD in all 28 forms; no scratch and no VGPR spill in any. 15 of the 21 forms with D > 1 hold more
+// Budgets, from the compiler's kernel-resource-usage remarks: LDS is the twiddle
+// tables of N, one padded image per team and (ROT) the 128-byte step table, 42.0 / 50.0 / 66.0 /
+// 132.0 KiB per workgroup at N = 1024 / 2048 / 4096 / 8192; 232 to 254 VGPRs (ROT = false: 220 to
+// 238), no AGPRs, two waves per SIMD in all forms; no scratch and no VGPR spill in any. 15 of the
+// 21 forms with D > 1 hold more
 // scalars than there are SGPRs and keep 30 to 38 of them in VGPR lanes (SGPR spill in the remarks; no
 // memory). The lane index is re-read through an empty asm before the fold (tq): with its addresses
 // hoisted out of the frame loop next to the forward transform's, the D > 1 forms took 256 VGPRs and up
@@ -74,17 +90,18 @@ struct args {
     const float2* hs;
 };
 using launch_fn = void (*)(const args&, unsigned grid, hipStream_t s);
-// the launcher of k_fft_xlat<N, D>, D in {1, 2, 4, 8, 16, 32, 64} (nsh_fft_xlat_<N>.hip)
+// the launcher of k_fft_xlat<N, D, rot>, D in {1, 2, 4, 8, 16, 32, 64}; rot = false (no rotation:
+// the caller's inc is 0) exists at D = 1 only (nsh_fft_xlat_<N>.hip)
 template <int N>
-launch_fn launcher(int D);
+launch_fn launcher(int D, bool rot);
 template <>
-launch_fn launcher<1024>(int D);
+launch_fn launcher<1024>(int D, bool rot);
 template <>
-launch_fn launcher<2048>(int D);
+launch_fn launcher<2048>(int D, bool rot);
 template <>
-launch_fn launcher<4096>(int D);
+launch_fn launcher<4096>(int D, bool rot);
 template <>
-launch_fn launcher<8192>(int D);
+launch_fn launcher<8192>(int D, bool rot);
 
 // team_sync calls of fft_team<n, INV>, n > 16
 constexpr int team_syncs(int n)
@@ -97,7 +114,7 @@ constexpr int team_syncs(int n)
 template <int N>
 constexpr bool hs_in_regs = geom<N>::NT <= 256;
 
-template <int N, int D>
+template <int N, int D, bool ROT = true>
 __global__ __launch_bounds__(geom<N>::NT) void k_fft_xlat(const float2* __restrict__ in, const float2* __restrict__ hist_in,
                                                           float2* __restrict__ hist_out, float2* __restrict__ out,
                                                           int64_t n_out, int L, int O, uint64_t inc, uint64_t first,
@@ -116,9 +133,11 @@ __global__ __launch_bounds__(geom<N>::NT) void k_fft_xlat(const float2* __restri
     // of the inverse sits c(m) outputs after the lane's first (store_frame)
     __shared__ float2 steps[16];
     nsh::fft::stage_table(tw, tw_g, G::TWN, threadIdx.x, G::NT);
-    if (threadIdx.x < 16) {
-        const int m = threadIdx.x;
-        steps[m] = nsh::phasor((uint64_t)(GM::TT * (m % GM::NBL) + GM::QL * (m / GM::NBL)) * ((uint64_t)D * inc));
+    if constexpr (ROT) {
+        if (threadIdx.x < 16) {
+            const int m = threadIdx.x;
+            steps[m] = nsh::phasor((uint64_t)(GM::TT * (m % GM::NBL) + GM::QL * (m / GM::NBL)) * ((uint64_t)D * inc));
+        }
     }
     __syncthreads();
     const int t = threadIdx.x & (G::TT - 1), team = threadIdx.x / G::TT;
@@ -156,7 +175,7 @@ __global__ __launch_bounds__(geom<N>::NT) void k_fft_xlat(const float2* __restri
         int64_t items = n_out - o0;
         items = items < 0 ? 0 : (items > Vd ? Vd : items);
         const __amdgpu_buffer_rsrc_t r = span_rsrc(out + (items > 0 ? o0 : 0), items);
-        if (inc == 0) {
+        if (!ROT || inc == 0) {
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
                 const int i = GM::out_idx(t, m);
@@ -270,18 +289,19 @@ __global__ __launch_bounds__(geom<N>::NT) void k_fft_xlat(const float2* __restri
     if (blockIdx.x == 0) nsh::store_history<G::NT>(in, hist_in, hist_out, n_in, L, threadIdx.x);
 }
 
-template <int N, int D>
+template <int N, int D, bool ROT = true>
 void launch_form(const args& a, unsigned grid, hipStream_t s)
 {
-    nsh::launch((k_fft_xlat<N, D>), dim3(grid), dim3(geom<N>::NT), 0, s, a.in, a.hist_in, a.hist_out, a.out, a.n_out, a.L, a.O,
+    nsh::launch((k_fft_xlat<N, D, ROT>), dim3(grid), dim3(geom<N>::NT), 0, s, a.in, a.hist_in, a.hist_out, a.out, a.n_out, a.L, a.O,
                 a.inc, a.first, a.tw, a.hs);
 }
 
 // the body of launcher<N>, for the one file that instantiates N's forms
 #define NSH_FFT_XLAT_FORMS(N)                                                                                                  \
     template <>                                                                                                                \
-    nsh::fxlat::launch_fn nsh::fxlat::launcher<N>(int D)                                                                       \
+    nsh::fxlat::launch_fn nsh::fxlat::launcher<N>(int D, bool rot)                                                             \
     {                                                                                                                          \
+        if (!rot) return D == 1 ? launch_form<N, 1, false> : nullptr;                                                          \
         switch (D) {                                                                                                           \
         case 1: return launch_form<N, 1>;                                                                                      \
         case 2: return launch_form<N, 2>;                                                                                      \

@@ -1,5 +1,5 @@
 // The 64-bit phase's phasor, shared by the rotating kernels (k_rotate and k_fir_xlat in
-// nsh_xlat.hip, k_fft_xlat in nsh_fft_xlat.hip); nsh_xlat.hip's header comment has the phase's
+// nsh_xlat.hip, k_fft_xlat in nsh_fft_xlat_kernel.hpp); nsh_xlat.hip's header comment has the phase's
 // definition. gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -45,6 +45,7 @@ using nsh::fft::geom;
 using nsh::fft::pad;
 using nsh::fft::pass_tables;
 using nsh::fft::team_sync;
+using nsh::fft::to_device;
 
 // bytes from base on, at most kSpan; built from wave-uniform values only (chunk_rsrc)
 constexpr int64_t kSpan = 0x70000000;
@@ -331,15 +332,9 @@ int nsh_psd_plan_create(int dev, int fft_size, int navg, const float* window_hos
     default: setup<8192>(p.get()); break;
     }
     NSH_CK(hipSetDevice(dev));
-    const std::vector<float2> h = pass_tables(fft_size);
-    if (!h.empty()) {
-        NSH_CK(hipMalloc(&p->tw, h.size() * sizeof(float2)));
-        NSH_CK(hipMemcpy(p->tw, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    }
-    if (window_host) {
-        NSH_CK(hipMalloc(&p->win, fft_size * sizeof(float)));
-        NSH_CK(hipMemcpy(p->win, window_host, fft_size * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if (const int rc = to_device(pass_tables(fft_size), &p->tw)) return rc;
+    if (window_host)
+        if (const int rc = to_device(std::vector<float>(window_host, window_host + fft_size), &p->win)) return rc;
     if (p->nseg > 1) {
         const int64_t row_bytes = (int64_t)fft_size * 4;
         int64_t vecs = env_int("NSH_PSD_SCRATCH_BYTES", kScratchBytes) / (row_bytes * p->nseg);

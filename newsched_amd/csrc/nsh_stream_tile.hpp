@@ -4,7 +4,7 @@
 // Device pieces first (they take tid as a parameter: reading threadIdx.x again in a helper moves the
 // callers' code), then the plans' common part and the entry points' argument checks. All four use
 // fma2, the plan base and, but for nsh_arb_resamp_ccf, the checks; stage_window serves k_resamp and
-// k_arb, store_history k_pfb, k_resamp and k_fft_filter (nsh_fft_filter.hip), store_tile k_resamp and k_arb. A kernel that keeps a loop
+// k_arb, store_history k_pfb, k_resamp and k_fft_xlat (nsh_fft_xlat_kernel.hpp), store_tile k_resamp and k_arb. A kernel that keeps a loop
 // of its own says at the loop what the shared one cost it (assembly or time).
 #pragma once
 #include "nsh_common.hpp"

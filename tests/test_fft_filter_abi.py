@@ -69,6 +69,25 @@ def test_create_refuses_taps_longer_than_half_a_frame(size, L):
     assert not h.value
 
 
+def test_without_a_device_create_fails_where_the_xlat_plan_is_made():
+    """The two entry points share one plan and differ in this: nsh_fft_filter_plan_create needs its
+    device at once, nsh_fft_xlat_plan_create makes the plan and uploads on first use."""
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("needs a machine without a device")
+    L = nsh.lib()
+    t = np.ones(127, np.complex64)
+    rc, h = create(t)
+    assert rc != 0 and not h.value
+    assert b"hipSetDevice(dev)" in L.nsh_last_error()  # HIP's own error, after every refusal of the arguments
+    x = C.c_void_p()
+    arr = t.view(np.float32).ctypes.data_as(C.POINTER(C.c_float))
+    assert L.nsh_fft_xlat_plan_create(0, arr, t.size, 1, 0.0, 0, C.byref(x)) == 0 and x.value
+    assert L.nsh_fft_xlat_valid(x) == 1024 - 126
+    assert L.nsh_fft_xlat_plan_destroy(x) == 0
+
+
 def test_run_refusals_in_order():
     L = nsh.lib()
     run = L.nsh_fft_filter_ccc

@@ -1,4 +1,4 @@
-"""GPU: nsh_fft_filter_ccc (k_fft_filter<N>, overlap-save FIR with complex taps) at its four frame
+"""GPU: nsh_fft_filter_ccc (k_fft_xlat<N, 1, false>, overlap-save FIR with complex taps) at its four frame
 sizes through the fft_size override and under the default size rule on each side of its boundaries.
 
 Reference (float64, in this file): numpy.convolve of hist_in ++ in with the taps, both complex128.
@@ -142,7 +142,7 @@ def test_parity(torch_cuda, N, Lk, kind):
     L = {"1": 1, "2": 2, "127": 127, "N/2-1": N // 2 - 1, "N/2": N // 2}[Lk]
     h = taps_of(kind, L)
     p = nsh.FftFilterPlan(h, N)
-    assert (p.fft_size, p.valid, p.hist_len, p.kernel) == (N, N - (L - 1), L - 1, f"k_fft_filter<{N}>")
+    assert (p.fft_size, p.valid, p.hist_len, p.kernel) == (N, N - (L - 1), L - 1, f"k_fft_xlat<{N}, 1, false>")
     x = uniform(sweep_len(p), N + L)
     check("parity " + kind, p, x, h, run(torch_cuda, p, x))
     p.close()
@@ -158,7 +158,7 @@ def test_default_size_rule(torch_cuda, L):
     assert lib.nsh_fft_filter_fft_size(p._h) == N
     assert lib.nsh_fft_filter_valid(p._h) == N - (L - 1)
     assert lib.nsh_fft_filter_history(p._h) == L - 1
-    assert lib.nsh_fft_filter_kernel(p._h) == b"k_fft_filter<%d>" % N
+    assert lib.nsh_fft_filter_kernel(p._h) == b"k_fft_xlat<%d, 1, false>" % N
     assert lib.nsh_fft_filter_tile(p._h) == max(1, 4096 // N)
     x = uniform(sweep_len(p), 7 + L)
     check("default rule", p, x, h, run(torch_cuda, p, x))
@@ -242,6 +242,22 @@ def test_grid_cap_does_not_change_the_bits(torch_cuda, N):
     p.grid_cap(0)
     assert np.array_equal(bits(run(torch_cuda, p, x)), bits(y0))
     check("grid cap", p, x, h, y0)
+    p.close()
+
+
+@pytest.mark.parametrize("N", [1024, 8192])  # Hs in registers, Hs re-read every frame
+def test_one_history_sample_at_the_frame_zero_seam(torch_cuda, N):
+    """L = 2: H = 1, so frame 0's window is exactly one history sample (non-zero here) and then the
+    input. One workgroup walks 2 tile + 1 frames: frame 0, a prefetched second trip and a partial
+    last frame. An overlap or a first index other than L - 1 and 0 shows at out[0] and at every frame
+    start; run checks hist_out's bits."""
+    h = taps_of("random", 2)
+    p = nsh.FftFilterPlan(h, N)
+    assert (p.valid, p.hist_len) == (N - 1, 1)
+    p.grid_cap(1)
+    x = uniform(2 * p.tile * p.valid + 17, 35 + N)
+    hist = np.array([3.0 - 2.0j], np.complex64)
+    check("frame-0 seam", p, x, h, run(torch_cuda, p, x, hist), hist)
     p.close()
 
 

@@ -1,4 +1,4 @@
-"""Kernel-level timing of fft_filter_ccc (k_fft_filter<N>) against its comparators, every comparison
+"""Kernel-level timing of fft_filter_ccc (k_fft_xlat<N, 1, false>) against its comparators, every comparison
 interleaved in one process. Each time is the kernel's own: an event pair armed with
 nsh_time_next_launch, recorded by the launch itself.
 
