@@ -40,9 +40,10 @@ def stats(y, r, frames):
     return math.sqrt(float(e2.mean())) / s, math.sqrt(float(e2.mean(axis=0).max())) / s
 
 
-def gate(name, y, model, r, frames):
-    """Print y's and the model's (whole, worst) against r and assert y's within WHOLE and WORST times
-    the model's. Returns the six figures (kernel whole, model whole, ratio, the same for worst)."""
+def gate(name, y, model, r, frames, whole=WHOLE, worst=WORST):
+    """Print y's and the model's (whole, worst) against r and assert y's within `whole` and `worst` times
+    the model's (the FFT family's WHOLE and WORST unless given: tests/fir_accuracy.py passes its own).
+    Returns the six figures (kernel whole, model whole, ratio, the same for worst)."""
     positions = np.asarray(r).size // frames
     assert frames >= MIN_FRAMES and frames * positions >= MIN_OUTPUTS, (name, frames, positions)
     wk, pk = stats(y, r, frames)
@@ -50,9 +51,9 @@ def gate(name, y, model, r, frames):
     print("RATIO accuracy whole kernel %.3g model %.3g ratio %.3f worst kernel %.3g model %.3g ratio %.3f %s"
           % (wk, wm, wk / wm, pk, pm, pk / pm, name))
     failed = []
-    if not wk <= WHOLE * wm:
-        failed.append("whole %.3g > %.2f x %.3g" % (wk, WHOLE, wm))
-    if not pk <= WORST * pm:
-        failed.append("worst position %.3g > %.2f x %.3g" % (pk, WORST, pm))
+    if not wk <= whole * wm:
+        failed.append("whole %.3g > %.2f x %.3g" % (wk, whole, wm))
+    if not pk <= worst * pm:
+        failed.append("worst position %.3g > %.2f x %.3g" % (pk, worst, pm))
     assert not failed, "%s: %s" % (name, "; ".join(failed))
     return wk, wm, wk / wm, pk, pm, pk / pm

@@ -31,6 +31,8 @@ q-ascending accumulation of the longest sum each kernel can have, on these taps,
 worst err / (1e-5 |ref| + 1e-6 scale) over 2048 outputs: xlat (1024 terms) 0.22, resamp (1024) 0.18,
 arb (1024) 0.18, pfb (32 terms, 32 branches) 0.06. It asserts at most 0.5: a correct fp32 kernel in
 the plainest order uses less than half of the tolerance, so a failing float case is the kernel's.
+That margin is also what tol_ok cannot see into: tests/test_gpu_fir_accuracy.py gates the same kernels'
+rms error, whole and per position, against fp32 models in these orders (tests/fir_accuracy.py).
 
 No case here depends on k_fir_xlat's Lc being a multiple of 8: the walk takes the taps at a part's
 edges one by one wherever the part starts, so no output depends on it; it is an alignment choice.
@@ -42,6 +44,9 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+# the float64 references per output and the fp32 emulation, shared with the accuracy gate
+from tests.fir_accuracy import (_emulate, _fma32, arb_indices, arb_ref, ceil_div, diff_taps, pfb_ref, phasors, resamp_ref,
+                                xlat_ref)
 
 gpu = pytest.mark.gpu
 
@@ -60,10 +65,6 @@ def host(t):
 
     torch.cuda.synchronize()
     return t.cpu().numpy()
-
-
-def ceil_div(a, b):
-    return -(-a // b)
 
 
 # ---- the dispatch, restated ------------------------------------------------------------------
@@ -387,93 +388,6 @@ def run_call(torch, n_items, H, off, call, aligned=None):
     return y[o:o + n_items].copy(), host(dho)[:H].copy()
 
 
-# ---- the references, float64, per output ------------------------------------------------------------
-def phasors(first, n, inc):
-    idx = (np.uint64(first % 2 ** 64) + np.arange(n, dtype=np.uint64))      # wraps mod 2^64
-    p = idx * np.uint64(inc)
-    turns = (p >> np.uint64(11)).astype(np.float64) / 2.0 ** 53
-    return np.exp(2j * np.pi * turns)
-
-
-def xlat_ref(x, hist, taps, D, inc, first, n_out):
-    """y[m] = sum_k h[k] rot(x)[mD - k]; hist = the L-1 raw samples before x[0]."""
-    L = len(taps)
-    ext = np.concatenate([hist.astype(np.complex128), x.astype(np.complex128)])
-    with np.errstate(over="ignore"):
-        ext = ext * phasors(first - (L - 1), ext.size, inc)
-    return np.convolve(ext, np.asarray(taps, np.float64))[L - 1::D][:n_out]
-
-
-def resamp_ref(x, hist, taps, I, D, n_units):
-    """y[n] = sum_q h[phi + q I] x[j0 - q], phi = (n D) mod I, j0 = floor(n D / I); hist = the Q-1 samples before x[0]."""
-    L = len(taps)
-    Q = ceil_div(L, I)
-    H = Q - 1
-    ext = np.concatenate([hist.astype(np.complex128), x[:n_units * D].astype(np.complex128)])
-    h = np.zeros(Q * I)
-    h[:L] = taps
-    n = np.arange(n_units * I)
-    j0, phi = n * D // I, n * D % I
-    y = np.zeros(n.size, np.complex128)
-    for q in range(Q):
-        y += h[phi + q * I] * ext[H + j0 - q]
-    return y
-
-
-def arb_indices(step, F, phase, n_out):
-    """i, j (int64) and mu (float32, as the kernel forms it) of the outputs 0 .. n_out-1."""
-    pos = np.uint64(phase) + np.arange(n_out, dtype=np.uint64) * np.uint64(step)   # below 2^57 here
-    k = (pos >> np.uint64(32)).astype(np.int64)
-    frac = (pos & np.uint64(0xffffffff)).astype(np.uint32)
-    mu = (frac >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    return k // F, k % F, mu
-
-
-def diff_taps(taps):
-    t = np.asarray(taps, np.float32)
-    return np.concatenate([t[1:] - t[:-1], np.zeros(1, np.float32)]).astype(np.float32)
-
-
-def arb_ref(x, hist, taps, F, step, phase, n_out):
-    """y[n] = sum_q (h[j + q F] + mu d[j + q F]) x[i - q] over j + q F < L; hist = the Q-1 samples before x[0]."""
-    L = len(taps)
-    Q = ceil_div(L, F)
-    H = Q - 1
-    i, j, mu = arb_indices(step, F, phase, n_out)
-    assert i.max() < x.size
-    ext = np.concatenate([hist.astype(np.complex128), x.astype(np.complex128)])
-    h = np.asarray(taps, np.float64)
-    d = diff_taps(taps).astype(np.float64)
-    mu = mu.astype(np.float64)
-    y = np.zeros(n_out, np.complex128)
-    for q in range(Q):
-        t = j + q * F
-        tc = np.minimum(t, L - 1)
-        y += np.where(t < L, (h[tc] + mu * d[tc]) * ext[i - q + H], 0)
-    return y
-
-
-def pfb_ref(x, hist, taps, M, n_out):
-    """(n_out, M): y[m][c] = sum_p u_p[m] exp(2j pi c p / M), u_p[m] = sum_q h[p + q M] x[(m - q) M - p];
-    hist = the L-1 samples before x[0]. Channels 0 and M/2 are the plain and the alternating sum of
-    the branches: exact on integer data."""
-    L = len(taps)
-    Q = ceil_div(L, M)
-    ext = np.concatenate([np.zeros(Q * M, np.complex128), hist.astype(np.complex128), x.astype(np.complex128)])
-    at0 = Q * M + L - 1                                   # x[0]
-    h = np.zeros(Q * M)
-    h[:L] = taps
-    m, p = np.arange(n_out)[:, None], np.arange(M)[None, :]
-    u = np.zeros((n_out, M), np.complex128)
-    for q in range(Q):
-        u += h[p + q * M] * ext[at0 + (m - q) * M - p]
-    c = np.arange(M)
-    y = u @ np.exp(2j * np.pi * ((p.T * c[None, :]) % M) / M)
-    y[:, 0] = u.sum(axis=1)
-    y[:, M // 2] = (u * (1 - 2 * (p % 2))).sum(axis=1)
-    return y
-
-
 def test_stream_forms_references_are_the_definitions():
     """The per-output references against the definitions the four older GPU files use (zero-stuff and
     convolve; one modulated convolution per channel), at small shapes."""
@@ -513,22 +427,6 @@ def test_stream_forms_references_are_the_definitions():
 
 
 # ---- CPU: the reference alone stays inside the tolerance ---------------------------------------------
-def _fma32(a, b, acc):
-    """fl32(a b + acc) for fp32 a, b, acc: the product is exact in double, one further rounding."""
-    return (a.astype(np.float64) * b.astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
-
-
-def _emulate(w, xw):
-    """Row-wise fp32 sums of w[:, q] xw[:, q], q ascending, one FMA per component and term."""
-    re = np.zeros(xw.shape[0], np.float32)
-    im = np.zeros(xw.shape[0], np.float32)
-    xr, xi = np.ascontiguousarray(xw.real), np.ascontiguousarray(xw.imag)
-    for q in range(xw.shape[1]):
-        re = _fma32(w[:, q], xr[:, q], re)
-        im = _fma32(w[:, q], xi[:, q], im)
-    return re + 1j * im.astype(np.float64)
-
-
 def _margin(y, ref):
     err, scale = np.abs(y - ref), np.max(np.abs(ref))
     return float(np.max(err / (1e-5 * np.abs(ref) + 1e-6 * scale)))
