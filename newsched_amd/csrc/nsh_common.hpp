@@ -157,14 +157,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const float2* base,
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, bytes, 0x00020000);
 }
 constexpr int AUX_NT = 2; // gfx950 cache policy bits: nt (streaming)
-// streaming loads / stores (ablation builds override: tools/probe/build_file_abl.sh)
-#ifndef NSH_AUX_LD
-#define NSH_AUX_LD 2
-#endif
-#ifndef NSH_AUX_ST
-#define NSH_AUX_ST 2
-#endif
-constexpr int AUX_LD = NSH_AUX_LD, AUX_ST = NSH_AUX_ST;
+constexpr int AUX_LD = 2, AUX_ST = 2; // streaming loads / stores
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float buf_f4 __attribute__((ext_vector_type(4)));

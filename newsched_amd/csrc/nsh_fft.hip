@@ -50,37 +50,28 @@ __device__ __forceinline__ cf cmul_rn(cf a, cf b)
 }
 constexpr int WLDS = nsh::fft::padded(N); // one wave's padded image
 
-// The passes' twiddles, staged per workgroup. Read from the natural 1024-entry table (the default),
-// pass 2's W_1024^{4 k r} (k = lane & 15) puts the 16 lanes of a read group at stride 4 r entries --
-// 4- to 16-way LDS bank conflicts (PMC: 36 % of the channelizer's LDS-active cycles are conflict
-// cycles) -- and pass 3's W^{2 j'} at stride 2. NSH_FFT_TW_READORDER=1 (a probe, round 6) stages them
-// in the order the lanes read them instead, the same floats (bit-identical outputs):
-//   T2[r][k]      = W_1024^{4 k r}   (r, k < 16: a read group's lanes take 16 consecutive entries)
-//   T3[r - 1][j'] = W_1024^{r j'}    (r = 1..3, j' < 256: consecutive lanes, consecutive entries)
-// Conflict-free, and no faster: channelizer 765-769 vs 763-764 us, fft1024 707-708 vs 704 us per
-// 2^28 samples, both orders (profiles/r06e_chan_twiddle_layout_ab.log) -- LDS does not bound them.
-#ifndef NSH_FFT_TW_READORDER
-#define NSH_FFT_TW_READORDER 0
-#endif
-constexpr int T2N = 16 * 16, T3N = 3 * 256, TWN = NSH_FFT_TW_READORDER ? T2N + T3N : N;
+// The passes' twiddles, staged per workgroup in the natural 1024-entry table. Pass 2's W_1024^{4 k r}
+// (k = lane & 15) puts the 16 lanes of a read group at stride 4 r entries -- 4- to 16-way LDS bank
+// conflicts (PMC: 36 % of the channelizer's LDS-active cycles are conflict cycles) -- and pass 3's
+// W^{2 j'} at stride 2. Staged in the order the lanes read them instead (T2[r][k] = W^{4 k r},
+// T3[r - 1][j'] = W^{r j'}) the reads are conflict-free and no faster: channelizer 765-769 vs
+// 763-764 us, fft1024 707-708 vs 704 us per 2^28 samples, both orders
+// (profiles/r06e_chan_twiddle_layout_ab.log) -- LDS does not bound them.
+constexpr int TWN = N;
 __device__ __forceinline__ void stage_twiddles(cf* __restrict__ t, const float2* __restrict__ tw_g, int tid, int nt)
 {
-    if (!NSH_FFT_TW_READORDER) return nsh::fft::stage_table(t, tw_g, TWN, tid, nt);
-    for (int i = tid; i < TWN; i += nt) {
-        const int e = i < T2N ? (4 * (i & 15) * (i >> 4)) & (N - 1) : ((1 + (i - T2N) / 256) * ((i - T2N) & 255)) & (N - 1);
-        t[i] = cf{ tw_g[e].x, tw_g[e].y };
-    }
+    nsh::fft::stage_table(t, tw_g, TWN, tid, nt);
 }
 // pass 2's W_1024^{4 k2 r} and pass 3's W_1024^{r jp} (r = 1..3) from the staged table
 template <bool INV>
 __device__ __forceinline__ cf tw_pass2(const cf* __restrict__ tw, int k2, int r)
 {
-    return conj_if<INV>(NSH_FFT_TW_READORDER ? tw[16 * r + k2] : tw[(4 * k2 * r) & (N - 1)]);
+    return conj_if<INV>(tw[(4 * k2 * r) & (N - 1)]);
 }
 template <bool INV>
 __device__ __forceinline__ cf tw_pass3(const cf* __restrict__ tw, int jp, int r)
 {
-    return conj_if<INV>(NSH_FFT_TW_READORDER ? tw[T2N + 256 * (r - 1) + jp] : tw[(r * jp) & (N - 1)]);
+    return conj_if<INV>(tw[(r * jp) & (N - 1)]);
 }
 
 // Transform of one frame held as v[m] = x[lane + 64 m]; on return v[m] = X[lane + 64 m]
@@ -165,20 +156,11 @@ __global__ __launch_bounds__(NT) void k_fft1024(const float2* __restrict__ in, f
 // weights in LDS the kernel fits 168 VGPRs, i.e. 3 workgroups (12 waves) per CU, and that
 // occupancy hides the load latency better: 816 vs 858 us per 2^28 samples
 // (tools/probe/fft_ab.py history in DESIGN.md section 4).
-#ifndef NSH_CHAN_FPW
-#define NSH_CHAN_FPW 4
-#endif
-constexpr int CFPW = NSH_CHAN_FPW; // channelizer frames (waves) per workgroup
-// probe knobs (round 6): the next frame prefetched into registers as in k_fft1024, and the launch
-// bounds' minimum workgroups per CU (2 lets the compiler take up to 256 VGPRs: 2 waves per SIMD)
-#ifndef NSH_CHAN_PREFETCH
-#define NSH_CHAN_PREFETCH 0
-#endif
-#ifndef NSH_CHAN_MINWG
-#define NSH_CHAN_MINWG 2
-#endif
+constexpr int CFPW = 4; // channelizer frames (waves) per workgroup
+// the launch bounds' minimum workgroups per CU (2 lets the compiler take up to 256 VGPRs: 2 waves per SIMD)
+constexpr int CHAN_MINWG = 2;
 template <int FW>
-__global__ __launch_bounds__(64 * FW, FW == 4 ? NSH_CHAN_MINWG : 1) void k_chan1024(const float2* __restrict__ in, float2* __restrict__ out, int64_t nframes,
+__global__ __launch_bounds__(64 * FW, CHAN_MINWG) void k_chan1024(const float2* __restrict__ in, float2* __restrict__ out, int64_t nframes,
                                                     const float2* __restrict__ tw_g, const float2* __restrict__ w)
 {
     __shared__ cf tw[TWN];
@@ -191,22 +173,6 @@ __global__ __launch_bounds__(64 * FW, FW == 4 ? NSH_CHAN_MINWG : 1) void k_chan1
     const int j = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * FW;
     cf v[16];
-#if NSH_CHAN_PREFETCH
-    int64_t f = (int64_t)blockIdx.x * FW + (threadIdx.x >> 6);
-    if (f >= nframes) return;
-    cf nx[16];
-    load_frame16(v, in, f, nframes);
-    for (; f < nframes; f += stride) {
-        load_frame16(nx, in, f + stride, nframes);
-        fft_wave<false>(v, img, tw);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = cmul_rn(v[m], wl[j + 64 * m]);
-        fft_wave<true>(v, img, tw);
-        store_frame16(v, out, f, nframes);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = nx[m];
-    }
-#else
     for (int64_t f = (int64_t)blockIdx.x * FW + (threadIdx.x >> 6); f < nframes; f += stride) {
         load_frame16(v, in, f, nframes);
         fft_wave<false>(v, img, tw);
@@ -215,7 +181,6 @@ __global__ __launch_bounds__(64 * FW, FW == 4 ? NSH_CHAN_MINWG : 1) void k_chan1
         fft_wave<true>(v, img, tw);
         store_frame16(v, out, f, nframes);
     }
-#endif
 }
 
 std::mutex g_tw_mtx;
@@ -242,15 +207,7 @@ int twiddles(int dev, const float2** tw)
 // launch: 16384 workgroups run the channelizer 5 % faster (806 -> 754-774 us, 66.5 -> 69.4-71.2 %),
 // 24576 the fft1024 13 % faster (768 -> 670 us = 80 % of 8 TB/s); 65536 (one frame per wave, the
 // tables staged per frame) is slower for both (r05zt, r05zu: both orders, bit-identical).
-#ifndef NSH_FFT_CAP
-#define NSH_FFT_CAP 24576
-#endif
-#ifndef NSH_CHAN_CAP4
-#define NSH_CHAN_CAP4 16384
-#endif
-#ifndef NSH_CHAN_CAP
-#define NSH_CHAN_CAP (65536 / NSH_CHAN_FPW) // probe builds with NSH_CHAN_FPW != 4: the same frames per workgroup step
-#endif
+constexpr int FFT_CAP = 24576, CHAN_CAP = 16384;
 } // namespace
 
 extern "C" {
@@ -274,7 +231,7 @@ int nsh_channelizer1024(const float* in, float* out, const float* w, int64_t nfr
     NSH_CK(hipGetDevice(&dev));
     const float2* tw = nullptr;
     if (int rc = twiddles(dev, &tw)) return rc;
-    nsh::launch(k_chan1024<CFPW>, dim3(frame_grid(nframes, CFPW, CFPW == 4 ? NSH_CHAN_CAP4 : NSH_CHAN_CAP)), dim3(64 * CFPW), 0, nsh::S(stream),
+    nsh::launch(k_chan1024<CFPW>, dim3(frame_grid(nframes, CFPW, CHAN_CAP)), dim3(64 * CFPW), 0, nsh::S(stream),
                        (const float2*)in, (float2*)out, nframes, tw, (const float2*)w);
     NSH_CK_LAUNCH("nsh_channelizer1024");
     return 0;
@@ -288,7 +245,7 @@ int nsh::fft::fft1024_launch(const float2* in, float2* out, int64_t nframes, boo
     NSH_CK(hipGetDevice(&dev));
     const float2* tw = nullptr;
     if (int rc = twiddles(dev, &tw)) return rc;
-    const dim3 grid(frame_grid(nframes, FPW, cap > 0 ? cap : NSH_FFT_CAP));
+    const dim3 grid(frame_grid(nframes, FPW, cap > 0 ? cap : FFT_CAP));
     if (inverse)
         nsh::launch(k_fft1024<true>, grid, dim3(NT), 0, s, in, out, nframes, tw);
     else

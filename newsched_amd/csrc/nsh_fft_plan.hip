@@ -136,9 +136,7 @@ constexpr int default_cap(int n) { return n <= 1024 ? 8192 : n <= 4096 ? 2048 : 
 // sizes up to this one move their samples by linear accesses through the image (k_fft's LIN):
 // 168 against 1445 us per 2^26 samples at N = 16, 167 / 336 at 32, 166 / 216 at 64, 167 / 176 at 128,
 // 166 / 168 (within the spread) at 256 (tools/fft_bench.py --io-ab, profiles/fft_bench.json)
-#ifndef NSH_FFT_LIN_MAX
-#define NSH_FFT_LIN_MAX 128
-#endif
+constexpr int LIN_MAX = 128;
 constexpr int LIN_INST_MAX = 256; // ... and the largest size that instantiates it at all
 
 template <int N>
@@ -172,9 +170,9 @@ int nsh_fft_plan_create(int dev, int fft_size, int inverse, const float* window_
     p->inverse = inverse != 0;
     p->shift = shift != 0;
     p->plain1024 = fft_size == 1024 && !window_host && !shift;
-    p->cap_default = p->cap = p->plain1024 ? 0 : default_cap(fft_size); // 0: k_fft1024's own (NSH_FFT_CAP)
+    p->cap_default = p->cap = p->plain1024 ? 0 : default_cap(fft_size); // 0: k_fft1024's own (FFT_CAP)
     // NSH_FFT_IO=strided|linear overrides the size threshold (the A/B of tools/fft_bench.py)
-    bool lin = fft_size <= NSH_FFT_LIN_MAX && fft_size <= LIN_INST_MAX;
+    bool lin = fft_size <= LIN_MAX && fft_size <= LIN_INST_MAX;
     if (const char* e = std::getenv("NSH_FFT_IO")) {
         if (std::string(e) == "linear") lin = fft_size <= LIN_INST_MAX;
         if (std::string(e) == "strided") lin = false;

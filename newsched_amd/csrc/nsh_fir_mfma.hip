@@ -48,11 +48,10 @@ namespace {
 // Taps: v9 kept 2 x 2Q B fragments in VGPRs (80 registers, 20 KiB per wave from L2 at every
 // workgroup start -- in the probe, 20 KiB of such loads per chunk cost 10-40 %). Here the
 // fragments come from LDS: the scaled taps reversed, R[m] = h[32Q - 1 - m], hi and lo fp16
-// planes, stored as NSH_V12_COPIES = 4 copies shifted by 0..3 elements, so the 8 consecutive taps
-// a lane needs for one k-step (R[m0 .. m0 + 8)) are two aligned ds_read_b64 from copy m0 mod 4
-// (or, with 8 copies, one ds_read_b128 from copy m0 mod 8). Copy pitch = 64 mod 128 bytes: each
-// 32-lane group of a ds_read_b64 and each 16-lane group of a ds_read_b128 ({0-3,12-15,20-27},
-// {4-11,16-19,28-31}, and +32; MI355X_MICROARCH.md §LDS) hits distinct banks for every k-step and
+// planes, stored as 4 copies shifted by 0..3 elements, so the 8 consecutive taps
+// a lane needs for one k-step (R[m0 .. m0 + 8)) are two aligned ds_read_b64 from copy m0 mod 4.
+// Copy pitch = 64 mod 128 bytes: each 32-lane group of a ds_read_b64
+// (MI355X_MICROARCH.md §LDS) hits distinct banks for every k-step and
 // every Q (exhaustive check over pitches; the earlier 32 mod 64 pitch was 2-way on every tap
 // read, 35 % of the kernel's LDS cycles in profiles/r02f_pmc_fir.json). The image
 // (2 x 4 x (32Q + 32) fp16, 3 KiB at Q = 5) is prepared on the host and loaded per workgroup
@@ -60,51 +59,33 @@ namespace {
 // Scale and exact-path test cover the chunk and its halo. Results match v9 to within the
 // split's rounding (v9's scale also covered the whole previous chunk), not bit for bit.
 // Chunk order inside an XCD: workgroup k of an XCD's sequence filters chunk k (address order), or,
-// with NSH_V12_ROT (default), chunk k with its low two bits rotated by an xor-fold of k >> 2 (a
+// by default, chunk k with its low two bits rotated by an xor-fold of k >> 2 (a
 // bijection on every full group of 4, the order still ascending group by group). Without it, chunks
 // that need the exact path every 4th or 8th chunk were as slow as all-exact streams
 // (profiles/r02t_cliff_curve.log: k = 3 1381 us, k = 4 2775, k = 6 1260, k = 8 1602): consecutive
 // workgroups of an XCD are dealt out round-robin, so a power-of-two stride landed every slow chunk
 // on the same quarter of the XCD. Rotated: k = 4 1216 us, k = 8 957, k = 2 1703; main path
 // bit-identical, 718.0 vs 721.2 us (profiles/r02u_*).
-#ifndef NSH_V12_ROT
-#define NSH_V12_ROT 1
-#endif
 // Cache policy of the decimators' chunk loads. A thread loads its D float4 (2 D consecutive
 // samples) in D instructions, so one instruction's lanes are 16 D bytes apart and D instructions
 // touch the same lines: at D = 4 nontemporal loads fetched each line from L2 four times, the
 // default policy lets the later instructions hit L1 -- 642 -> 544 us per 2^28 inputs, 52 -> 62 %;
 // at D = 2 nontemporal stays faster (591 vs 638 us; profiles/r03w_v11_load_policy_ab.log).
-#ifndef NSH_V11_AUX2
-#define NSH_V11_AUX2 2 // nt
-#endif
-#ifndef NSH_V11_AUX4
-#define NSH_V11_AUX4 0 // default
-#endif
-#ifndef NSH_V12_F32T
-#define NSH_V12_F32T 1 // probe builds: 0 = finite wide-range chunks on the fp32 direct form
-#endif
-#ifndef NSH_V12_LDS_PAD
-#define NSH_V12_LDS_PAD 0 // probe builds: extra LDS per workgroup (fewer resident workgroups per CU)
-#endif
-// Shifted tap copies: 4, read as two ds_read_b64 per B fragment (8-B aligned), or 8, read as one
-// ds_read_b128 (16-B aligned). Four copies take 3.5 KiB instead of 7 at Q = 5, which brings the
+constexpr int V11_AUX2 = 2; // nt
+constexpr int V11_AUX4 = 0; // default
+// Shifted tap copies: 4, read as two ds_read_b64 per B fragment (8-B aligned); 8 copies would be read
+// as one ds_read_b128 (16-B aligned). Four copies take 3.5 KiB instead of 7 at Q = 5, which brings the
 // workgroup to 25.5 KiB of LDS: 6 resident workgroups per CU instead of 5 (LDS-bound; 72 VGPRs
 // would allow 7) -- the kernel's rate follows the chunks in flight per CU (5 -> 4 resident
 // workgroups: 734 -> 802 us per 2^28, profiles/r02j_v12_occupancy_ab.log).
-#ifndef NSH_V12_COPIES
-#define NSH_V12_COPIES 4
-#endif
-constexpr int v12_tw(int Q) { return 32 * Q + (NSH_V12_COPIES == 8 ? 24 : 32); } // fp16 per copy (multiple of 8)
-// Plane row pitch (32 fp16 samples = 64 B per row): 80 B (v9's padded rows) or 64 B with the
-// row's four 16-B chunks XOR-swizzled by (row >> 2) & 3. Either way each 16-lane group of an
-// A-fragment ds_read_b128 (16 consecutive rows, one chunk) hits 16 distinct 16-B slots; the
-// unpadded form takes 17 KiB instead of 22 for the four planes (20.5 KiB per workgroup with the
-// 4-copy tap image: 7 resident workgroups per CU, the 72-VGPR limit) but measured slower than 6
-// (732 vs 708-719 us, bit-identical; profiles/r02j_v12_occupancy_ab.log): 80 is the default.
-#ifndef NSH_V12_PITCH
-#define NSH_V12_PITCH 80
-#endif
+constexpr int V12_COPIES = 4;
+constexpr int v12_tw(int Q) { return 32 * Q + 32; } // fp16 per copy (multiple of 8)
+// Plane row pitch (32 fp16 samples = 64 B per row): 80 B (v9's padded rows), so that each 16-lane
+// group of an A-fragment ds_read_b128 (16 consecutive rows, one chunk) hits 16 distinct 16-B slots.
+// A 64-B pitch with the row's four 16-B chunks XOR-swizzled by (row >> 2) & 3 does the same in 17 KiB
+// instead of 22 for the four planes (20.5 KiB per workgroup with the 4-copy tap image: 7 resident
+// workgroups per CU, the 72-VGPR limit) but measured slower than 6 (732 vs 708-719 us,
+// bit-identical; profiles/r02j_v12_occupancy_ab.log).
 template <int Q>
 struct geom12 {
     static constexpr int NT = 256;
@@ -112,28 +93,21 @@ struct geom12 {
     static constexpr int H = 32 * (Q - 1);
     static constexpr int HP = H / 2;
     static constexpr int NB = (CHUNK + H) / 32;
-    static constexpr int PITCH = NSH_V12_PITCH;
+    static constexpr int PITCH = 80;
     static constexpr int PLANE = (NB * PITCH + 255) / 256 * 256;
     static constexpr int BUF = 4 * PLANE;
-    static constexpr int NCP = NSH_V12_COPIES;                       // shifted copies per plane
+    static constexpr int NCP = V12_COPIES;                           // shifted copies per plane
     static constexpr int TW = v12_tw(Q);                             // fp16 per shifted copy
     static constexpr int COPY = ((2 * TW + 63) / 128) * 128 + 64;    // bytes, = 64 mod 128, >= 2 TW
     static constexpr int TAPS = 2 * NCP * COPY;                      // [plane][shift] copies
     static constexpr int IMG_UNITS = 2 * NCP * TW / 8;               // 16-B units of the global image
     static constexpr int SLOTS = BUF + TAPS;                         // u32 max[4], mnz[4]
-    static constexpr int LDS = SLOTS + 32 + NSH_V12_LDS_PAD;
+    static constexpr int LDS = SLOTS + 32;
     static_assert(COPY >= 2 * TW && COPY % 128 == 64, "copy pitch");
     static_assert((HP + 4 * NT) * 16 <= BUF, "a raw fp32 chunk + halo fits the plane buffer");
     static_assert(HP <= NT, "halo pairs: one per thread");
-    static_assert(NCP == 4 || NCP == 8, "4 or 8 shifted tap copies");
-    static_assert(PITCH == 64 || PITCH == 80, "plane pitch");
     // byte offset of sample s (even) in a plane
-    static __device__ __forceinline__ int at(int s)
-    {
-        const int row = s >> 5;
-        if (PITCH == 80) return row * 80 + (s & 31) * 2;
-        return row * 64 + ((((s >> 3) & 3) ^ ((row >> 2) & 3)) << 4) + (s & 7) * 2;
-    }
+    static __device__ __forceinline__ int at(int s) { return (s >> 5) * PITCH + (s & 31) * 2; }
     static_assert(IMG_UNITS <= 2 * NT, "tap image: two 16-B units per thread at most");
 };
 
@@ -155,9 +129,9 @@ __device__ __forceinline__ void store_pair12(const float4& v, unsigned char* p, 
 }
 // The chunk (v: lane t holds samples (2t, 2t + 1) + 512 u) and its halo pair hv (tid < HP) -> the
 // split planes. One address per thread: sample H + 2 (tid + 256 u) lies 16 u rows below sample
-// H + 2 tid in the same column, so at the 80-B pitch unit u is stored at the thread's base plus
-// the constant 1280 u (= 5 x 256: with the planes a multiple of 256 B apart, every store of the
-// thread is an immediate of one ds_write2st64_b32 base). The swizzled 64-B pitch keeps at().
+// H + 2 tid in the same column, so unit u is stored at the thread's base plus the constant
+// 1280 u (= 5 x 256: with the planes a multiple of 256 B apart, every store of the thread is an
+// immediate of one ds_write2st64_b32 base).
 template <int Q, bool MUL>
 __device__ __forceinline__ void split_chunk12(unsigned char* lds, const float4 (&v)[4], const float4& hv, int tid, int sc)
 {
@@ -166,7 +140,7 @@ __device__ __forceinline__ void split_chunk12(unsigned char* lds, const float4 (
     unsigned char* base = lds + G::at(G::H + 2 * tid);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-        store_pair12<Q, MUL>(v[u], G::PITCH == 80 ? base + 16 * 80 * u : lds + G::at(G::H + 2 * (tid + G::NT * u)), sc);
+        store_pair12<Q, MUL>(v[u], base + 16 * G::PITCH * u, sc);
 }
 
 // Chunks the split cannot carry leave the bench kernel (round 4, verdict r03 item 4). A chunk
@@ -196,9 +170,7 @@ constexpr int XQ_N = 64;                   // sub-queues (one counter each)
 constexpr int XQ_LINE = 64;                // words between counters (256 B)
 constexpr int XQ_E = XQ_N * XQ_LINE;       // first entry word
 __host__ __device__ constexpr int64_t xq_subcap(int64_t grid) { return (grid + XQ_N - 1) / XQ_N; }
-#ifndef NSH_X12_PER_CU
-#define NSH_X12_PER_CU 5 // k_fir_exact12 workgroups per CU (a persistent walk over the queue) = its waves per SIMD
-#endif
+constexpr int X12_PER_CU = 5; // k_fir_exact12 workgroups per CU (a persistent walk over the queue) = its waves per SIMD
 
 // A main kernel's workgroup queues chunk ch (m: its largest magnitude, non-finite -> the direct
 // form) for the launch's exact kernel: a vector atomic and a vector store, from one lane.
@@ -230,7 +202,10 @@ struct xq_reader {
         : xq(xq_), subcap(subcap_)
     {
         const int lane = tid & 63;
-        if (blockIdx.x == 0 && tid < 64) // the next launch's counters (vector stores, one lane each)
+        // the next launch's counters (vector stores, one lane each). & and not &&: whether the compiler
+        // folds the short-circuit form into one test depends on unrelated code, and unfolded it loses
+        // tid's range (a 64-bit store address, wider masks in the kernels below)
+        if ((blockIdx.x == 0) & (tid < 64))
             __hip_atomic_store(xq_next + XQ_LINE * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // every wave: the XQ_N counters (one per lane) and their inclusive prefix sum
         incl = __hip_atomic_load(xq + XQ_LINE * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -381,7 +356,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     const int64_t n_in = n_out;
     const int64_t nchunks = (n_out + G::CHUNK - 1) / G::CHUNK;
     int64_t wi = blockIdx.x >> 3; // this workgroup's place in its XCD's sequence
-#if NSH_V12_ROT
     if ((wi | 3) < per_x) { // full aligned group of 4: rotate it by an xor-fold of the group index
         const uint64_t grp = (uint64_t)wi >> 2;
         unsigned r = (unsigned)grp ^ (unsigned)(grp >> 32);
@@ -391,7 +365,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
         r ^= r >> 2;
         wi = (wi & ~(int64_t)3) | ((wi - (int64_t)r) & 3);
     }
-#endif
     const int64_t ch = (int64_t)(blockIdx.x & 7) * per_x + wi;
     if (ch >= nchunks) return; // whole workgroup: before any barrier
 
@@ -449,7 +422,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
         // lowest address (the last row pair, st >> 1 = Q - 1, first half), every step a compile-time
         // offset from it -- DS immediates are unsigned -- so the loop holds only LDS reads and MFMAs.
         const int b = rho & 15, c = rho >> 4;
-        const int row0 = (Q - 1) + 16 * wave + b; // A rows: row0 - (st >> 1); chunks h + 2 (st & 1)
+        // A rows: (Q - 1) + 16 wave + b - (st >> 1); chunks h + 2 (st & 1)
         const unsigned char* a_lo = lds + c * 2 * G::PLANE + (16 * wave + b) * G::PITCH + 16 * h;
         // taps h[t0 - j], t0 = i - 16 (st & 1) - 8 h + 32 (st >> 1): R[m0 + j], m0 = 32Q - 1 - t0 =
         // m_lo + 16 (st & 1) + 32 (Q - 1 - (st >> 1)) with m_lo = 31 - rho + 8 h >= 0. Every step moves
@@ -462,34 +435,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 #pragma unroll
         for (int st = 0; st < 2 * Q; ++st) {
             const int up = (Q - 1) - (st >> 1); // row pairs above the lowest
-            const unsigned char* ap;
-            if (G::PITCH == 80) {
-                ap = a_lo + 80 * up + 32 * (st & 1);
-            } else {
-                const int row = row0 - (st >> 1);
-                ap = lds + c * 2 * G::PLANE + row * 64 + (((h + 2 * (st & 1)) ^ ((row >> 2) & 3)) << 4);
-            }
+            const unsigned char* ap = a_lo + G::PITCH * up + 32 * (st & 1);
             const f16x8 A0 = *reinterpret_cast<const f16x8*>(ap);
             const f16x8 A1 = *reinterpret_cast<const f16x8*>(ap + G::PLANE);
             const unsigned char* tp = t_lo + 2 * (16 * (st & 1) + 32 * up);
-            f16x8 B0, B1;
-            if (G::NCP == 8) {
-                B0 = *reinterpret_cast<const f16x8*>(tp);
-                B1 = *reinterpret_cast<const f16x8*>(tp + G::NCP * G::COPY);
-            } else {
-                // four separate ds_read_b64 (the empty asm keeps the compiler from pairing
-                // them into ds_read2_b64, whose 16-lane groups conflict 2-way on this image)
-                const f16x4 b0 = *reinterpret_cast<const f16x4*>(tp);
-                asm volatile("" ::: "memory");
-                const f16x4 b1 = *reinterpret_cast<const f16x4*>(tp + 8);
-                asm volatile("" ::: "memory");
-                const f16x4 b2 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY);
-                asm volatile("" ::: "memory");
-                const f16x4 b3 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY + 8);
-                asm volatile("" ::: "memory"); // nor with the next step's: all steps read off one base now
-                B0 = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                B1 = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            // four separate ds_read_b64 (the empty asm keeps the compiler from pairing
+            // them into ds_read2_b64, whose 16-lane groups conflict 2-way on this image)
+            const f16x4 b0 = *reinterpret_cast<const f16x4*>(tp);
+            asm volatile("" ::: "memory");
+            const f16x4 b1 = *reinterpret_cast<const f16x4*>(tp + 8);
+            asm volatile("" ::: "memory");
+            const f16x4 b2 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY);
+            asm volatile("" ::: "memory");
+            const f16x4 b3 = *reinterpret_cast<const f16x4*>(tp + G::NCP * G::COPY + 8);
+            asm volatile("" ::: "memory"); // nor with the next step's: all steps read off one base now
+            const f16x8 B0 = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+            const f16x8 B1 = __builtin_shufflevector(b2, b3, 0, 1, 2, 3, 4, 5, 6, 7);
             acc_hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, B0, acc_hi, 0, 0, 0);
             acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, B1, acc_lo, 0, 0, 0);
             acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, B0, acc_lo, 0, 0, 0);
@@ -516,11 +477,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
     if (ch == 0) put_hist_tail<G::NT>(hist_out, in, hist_in, n_in, L); // after this workgroup's stores
 }
 
-// The chunks k_fir_mfma12 queued: a persistent walk over the queue (NSH_X12_PER_CU workgroups per
+// The chunks k_fir_mfma12 queued: a persistent walk over the queue (X12_PER_CU workgroups per
 // CU), one chunk per workgroup step, staged in the same LDS geometry (the fp32 tile's image fits
 // the planes + tap image; a raw fp32 chunk + halo fits the planes).
 template <int Q>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSH_X12_PER_CU))) void k_fir_exact12(const float2* __restrict__ in,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(X12_PER_CU))) void k_fir_exact12(const float2* __restrict__ in,
                                                     const float2* __restrict__ hist_in,
                                                     float2* __restrict__ out,
                                                     const float4* __restrict__ timg32, // exact-fp32 tile taps [4][TWF]
@@ -540,7 +501,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSH_X12_PER
         if ((int64_t)(e >> 1) >= q.nchunks) continue; // never for a queue this launch filled (defensive)
         float4 v[4], hv;
         load12<Q>(in, hist_in, L, n_out, e >> 1, v, hv);
-        exact_chunk12<Q>(lds, out, timg32, taps, L, n_out, e >> 1, v, hv, NSH_V12_F32T && !(e & 1u));
+        exact_chunk12<Q>(lds, out, timg32, taps, L, n_out, e >> 1, v, hv, !(e & 1u));
     }
 }
 
@@ -630,7 +591,7 @@ __device__ __forceinline__ void direct_tile11(const unsigned char* cur, const fl
 {
     using G = geom11<D, QH>;
     const int wave = ln.wave, g = ln.g, phase = ln.phase;
-    if constexpr (D == 4 || NSH_DECIM2_SHARED) {
+    if constexpr (D == 4) {
 #pragma unroll 1
         for (int t = 0; t < G::TILES; ++t) {
             nf2 acc[2];
@@ -725,7 +686,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
 #pragma unroll
             for (int f = 0; f < D; ++f) {
                 const nsh::buf_f4 t = __builtin_bit_cast(
-                    nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, ((tid + G::NT * u) * D + f) * 16, 0, D == 2 ? NSH_V11_AUX2 : NSH_V11_AUX4));
+                    nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, ((tid + G::NT * u) * D + f) * 16, 0, D == 2 ? V11_AUX2 : V11_AUX4));
                 v[u * D + f] = make_float4(t.x, t.y, t.z, t.w);
             }
     };
@@ -836,9 +797,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma11(const float2* __restrict_
 }
 
 // ---- k_fir_mfma13: the decimators' lockstep walk, exact chunks queued (round 5) ------------
-#ifndef NSH_V13_AUX // chunk loads' cache policy: nontemporal on whole-line loads (no line is read twice)
-#define NSH_V13_AUX (NSH_V13_CLOAD ? 2 : D == 2 ? NSH_V11_AUX2 : NSH_V11_AUX4)
-#endif
+constexpr int V13_AUX = 2; // chunk loads' cache policy: nontemporal on whole-line loads (no line is read twice)
 // k_fir_mfma11's per-chunk work (polyphase split at a per-chunk scale, the same MFMA tile) in a
 // different walk: the persistent workgroups of an XCD (x = blockIdx mod 8, W of them) take its
 // eighth of the chunks in lockstep -- at step i workgroup k of XCD x filters chunk
@@ -863,10 +822,8 @@ __device__ __forceinline__ void load13(const float2* __restrict__ in, const floa
     for (int u = 0; u < G::UNITS; ++u)
 #pragma unroll
         for (int f = 0; f < D; ++f) {
-            // NSH_V13_CLOAD: float4 q13(u, f) of the chunk (each instruction 1 KiB contiguous), else
-            // (tid + NT u) D + f (a thread's D float4 adjacent, each instruction spread over D KiB)
-            const int q = NSH_V13_CLOAD ? q13<D>(u, f) : (tid + G::NT * u) * D + f;
-            const nsh::buf_f4 t = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, q * 16, 0, NSH_V13_AUX));
+            // float4 q13(u, f) of the chunk (each instruction 1 KiB contiguous)
+            const nsh::buf_f4 t = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, q13<D>(u, f) * 16, 0, V13_AUX));
             v[u * D + f] = make_float4(t.x, t.y, t.z, t.w);
         }
     // the halo: input samples [ch CHUNK_IN - 2 HP, ch CHUNK_IN); a chunk index past the stream (an
@@ -1009,7 +966,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
     }
     nsh::lds_barrier();
     decision d_cur = decide(0, chunk_at(0));
-    if (!d_cur.ex) put_split11<D, QH, NSH_V13_CLOAD>(tid, lds, stash + G::HP, va, d_cur.s);
+    if (!d_cur.ex) put_split11<D, QH, true>(tid, lds, stash + G::HP, va, d_cur.s);
     load13<D, QH>(in, hist_in, L, n_in, chunk_at(1), va, ha);
     load13<D, QH>(in, hist_in, L, n_in, chunk_at(2), vb, hb);
     {
@@ -1032,7 +989,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
         unsigned char* nbuf = lds + pn * G::BUF;
         const decision d_nxt = decide(pn, chunk_at(i + 1));
         load13<D, QH>(in, hist_in, L, n_in, chunk_at(i + 3), ld, hld);
-        if (!d_nxt.ex) put_split11<D, QH, NSH_V13_CLOAD>(tid, nbuf, stash + pi * G::HP, nxt, d_nxt.s);
+        if (!d_nxt.ex) put_split11<D, QH, true>(tid, nbuf, stash + pi * G::HP, nxt, d_nxt.s);
         if (!d_cur.ex) {
             nf2 o[2 * G::TILES];
             mfma_tile(cur, -(d_cur.s + sh), o);
@@ -1060,7 +1017,7 @@ __global__ __launch_bounds__(256, 2) void k_fir_mfma13(const float2* __restrict_
 
 // The chunks k_fir_mfma13 queued, on the exact forms of k_fir_mfma11: finite -> the exact-fp32 tile
 // (filtered undecimated, every D-th output kept), inf/NaN -> the fp32 direct form. A persistent walk
-// over the queue (NSH_X12_PER_CU workgroups per CU), one chunk per workgroup step; it zeroes the next
+// over the queue (X12_PER_CU workgroups per CU), one chunk per workgroup step; it zeroes the next
 // launch's counters (k_fir_exact12's protocol).
 template <int D, int QH>
 __global__ __launch_bounds__(256) void k_fir_exact13(const float2* __restrict__ in,
@@ -1094,7 +1051,7 @@ __global__ __launch_bounds__(256) void k_fir_exact13(const float2* __restrict__ 
         const bool f32t = !(e & 1u);
         float4 v[4], hv;
         load13<D, QH>(in, hist_in, L, n_in, ch, v, hv);
-        auto q_of = [&](int u, int f) { return NSH_V13_CLOAD ? q13<D>(u, f) : (tid + G::NT * u) * D + f; }; // load13's float4
+        auto q_of = [&](int u, int f) { return q13<D>(u, f); }; // load13's float4
         nsh::lds_barrier(); // the previous chunk's reads of LDS are done
         stage_exact11<D, QH>(tid, lds, &hv, v, f32t, q_of);
         nsh::lds_barrier();
@@ -1228,7 +1185,7 @@ int launch_v13(const nsh_fir_plan* p, const float2* in, const float2* hin, float
     const int64_t grid = 8 * (int64_t)W;
     const int64_t steps = (per_x + W - 1) / W;
     const int64_t subcap = xq_subcap(grid) * steps; // a sub-queue's workgroups can queue every chunk they walk
-    const int64_t xcap = (int64_t)n_cu * NSH_X12_PER_CU;
+    const int64_t xcap = (int64_t)n_cu * X12_PER_CU;
     return launch_queued(
         p, s, subcap, "nsh_fir_ccf(mfma decim): exact queue", "nsh_fir_ccf(mfma decim v13)",
         "nsh_fir_ccf(mfma decim v13 exact chunks)",
@@ -1277,7 +1234,7 @@ int launch_v12(const nsh_fir_plan* p, const float2* in, const float2* hin, float
     const int64_t grid = per_x * 8;
     if (grid > 0x7fffffff) return nsh::fail_msg("nsh_fir_ccf(mfma v12): stream too long for one launch");
     const int64_t subcap = xq_subcap(grid);
-    const int64_t xcap = (int64_t)plan_cus(p) * NSH_X12_PER_CU;
+    const int64_t xcap = (int64_t)plan_cus(p) * X12_PER_CU;
     return launch_queued(
         p, s, subcap, "nsh_fir_ccf(mfma v12): exact queue", "nsh_fir_ccf(mfma fp16x2 v12)", "nsh_fir_ccf(mfma v12 exact chunks)",
         [&](unsigned* cur, hipEvent_t start) {
@@ -1323,13 +1280,11 @@ static hipError_t f32_tile_image(nsh_fir_plan* p, int QF)
 // bit D: decim D on the lockstep walk (k_fir_mfma13) -- D = 4 since round 5 (r05b), D = 2 since its
 // whole-line loads (1.6 % faster, also with exact chunks every 4th / 64th chunk, bit-identical on
 // finite input, r05zzg, r05zzh); 0 selects the contiguous walk k_fir_mfma11 (tests run both)
-#ifndef NSH_DEC_WALK_MASK
-#define NSH_DEC_WALK_MASK 20
-#endif
+constexpr int DEC_WALK_MASK = 20;
 int nsh_fir_mfma_prepare_decim(nsh_fir_plan* p)
 {
     const char* wm = std::getenv("NSH_DEC_WALK_MASK");
-    p->dec_walk = wm && *wm ? std::atoi(wm) : NSH_DEC_WALK_MASK;
+    p->dec_walk = wm && *wm ? std::atoi(wm) : DEC_WALK_MASK;
     const char* wg = std::getenv("NSH_WALK_WGPC"); // probes: resident workgroups per CU of the walk
     p->walk_wgpc = wg && std::atoi(wg) >= 1 && std::atoi(wg) <= 4 ? std::atoi(wg) : 2;
     // polyphase taps h'_0[j] = h[D j], h'_r[j] = h[D (j - 1) + r] (r >= 1, j >= 1)
@@ -1385,7 +1340,7 @@ int nsh_fir_mfma_prepare(nsh_fir_plan* p)
     const int sh = p->sh8 = tap_scale(p);
     {
         // v12 tap image: R[m] = h[32Q - 1 - m] (scaled, hi/lo fp16), copy k holds R[k .. k + TW)
-        const int TW = v12_tw(Q), NCP = NSH_V12_COPIES;
+        const int TW = v12_tw(Q), NCP = V12_COPIES;
         std::vector<_Float16> f12((size_t)2 * NCP * TW, (_Float16)0.f);
         for (int k = 0; k < NCP; ++k)
             for (int e = 0; e < TW; ++e) {

@@ -78,21 +78,13 @@ __device__ __forceinline__ nf2 scale2(float a, float b, int sc)
 // followed by a conversion: one v_fma_mix{lo,hi}_f16 per value, reading the fp32 sample and its
 // half of the packed hi word, in place of two v_cvt_f32_f16, a v_pk_add_f32 and a
 // v_cvt_pk_f16_f32 per pair. The compiler does not form it from C++ (it folds fma(-hi, 1, a) back
-// to the subtract): inline asm; NSH_SPLIT_FMA_MIX=0 builds the C++ form (probe builds compare the two).
-#ifndef NSH_SPLIT_FMA_MIX
-#define NSH_SPLIT_FMA_MIX 1
-#endif
+// to the subtract): inline asm.
 __device__ __forceinline__ void split_pair16(float a, float b, unsigned& hi, unsigned& lo)
 {
     const f16x2 h = __builtin_convertvector(f32x2{ a, b }, f16x2);
     hi = __builtin_bit_cast(unsigned, h);
-#if NSH_SPLIT_FMA_MIX
     asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(a), "v"(hi));
     asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(b), "v"(hi));
-#else
-    const f32x2 r = f32x2{ a, b } - __builtin_convertvector(h, f32x2);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-#endif
 }
 
 // largest magnitude as a bit pattern: NaN-propagating v_maximum3_f32 with |.| operand modifiers
@@ -237,17 +229,11 @@ __device__ __forceinline__ void direct_tile9(const unsigned char* lds, const flo
 // loads/stores, LDS-only barriers. The halo (the D*H input samples before the chunk) is kept raw
 // in an LDS stash and split at each chunk's scale. What the two walks share is below; the walks
 // themselves and the exact forms are in nsh_fir_mfma.hip.
-#ifndef NSH_DECIM2_SHARED // A/B switch: D = 2 on the shared-input exact path (one pair at a time)
-#define NSH_DECIM2_SHARED 0
-#endif
-#ifndef NSH_V13_CLOAD
-// k_fir_mfma13: each chunk-load instruction reads 1 KiB contiguous (nontemporal), lane pairs exchange
-// their samples by DPP before the split stores; 0 = a thread's D float4 side by side (each
-// instruction spread over D KiB, default cache policy). D = 4, bit-identical: faster on three boxes
-// of four (72.5 vs 70.1 %, r05ze; ~1 % in four two-library A/Bs each on two more, r05zzd), 1.3 %
-// slower on one (r05zg)
-#define NSH_V13_CLOAD 1
-#endif
+// k_fir_mfma13 (CLOAD): each chunk-load instruction reads 1 KiB contiguous (nontemporal), lane pairs
+// exchange their samples by DPP before the split stores; k_fir_mfma11 keeps a thread's D float4 side
+// by side (each instruction spread over D KiB). On k_fir_mfma13 at D = 4, bit-identical: faster on
+// three boxes of four (72.5 vs 70.1 %, r05ze; ~1 % in four two-library A/Bs each on two more, r05zzd),
+// 1.3 % slower on one (r05zg)
 template <int D, int QH>
 struct geom11 {
     static constexpr int NT = 256;
@@ -262,10 +248,10 @@ struct geom11 {
     static constexpr int NB = (CHUNK + H) / 16;
     static constexpr int PLANE = NB * 32;
     static constexpr int IM_OFF = (2 * PLANE + 255) / 256 * 256 + 128;
-    // phase planes PH apart; k_fir_mfma13's split stores (NSH_V13_CLOAD) write all D phases in one
+    // phase planes PH apart; k_fir_mfma13's split stores (CLOAD) write all D phases in one
     // instruction, 32 / D pairs each per 32-lane group: PH = 32 * (4 / D) mod 128 B puts them on
     // disjoint banks
-    static constexpr int PH = (IM_OFF + 2 * PLANE + 255) / 256 * 256 + (NSH_V13_CLOAD ? 128 / D : 0);
+    static constexpr int PH = (IM_OFF + 2 * PLANE + 255) / 256 * 256 + 128 / D;
     static constexpr int BUF = (D * PH + 255) / 256 * 256;
     static constexpr int HP = D * H / 2;                      // halo float4 (2 input samples each)
     static constexpr int STASH = HP * 16;
@@ -313,7 +299,7 @@ __device__ __forceinline__ void store_pair11(unsigned char* buf, int r, int s, n
 }
 
 // the chunk's float4 (2 input samples) a lane loads as its unit u, instruction f, with
-// NSH_V13_CLOAD: the wave's 64 D float4 of unit u in D contiguous 1 KiB runs
+// CLOAD: the wave's 64 D float4 of unit u in D contiguous 1 KiB runs
 template <int D>
 __device__ __forceinline__ int q13(int u, int f)
 {

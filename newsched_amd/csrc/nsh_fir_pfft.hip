@@ -19,7 +19,8 @@
 //
 // Kernels: k_fir_pfft2<16> (below; the default at P = 16 since round 5: no ring, two image sets, the
 // phase sum and the inverse pipelined into the next frames) and k_fir_pfft<P> (P = 8, and P = 16
-// with NSH_PFFT_FORM=1), which works as follows.
+// with NSH_PFFT_FORM=1), which works as follows. What the two share -- per-lane constants, frame scale,
+// passes 2-3 of the transform -- is written once, ahead of both.
 // Kernel k_fir_pfft<P>: one workgroup of P waves per CU, walking a contiguous range of frames.
 //   * LDS ring of M rows x P samples (row = one P-sample input row, XOR-swizzled so that wave p
 //     reading phase p of 64 consecutive rows is bank-conflict-free); a frame shares Q rows with
@@ -48,6 +49,7 @@
 // oracle's double-accumulated cascade; north-star tolerance 1e-5).
 #include "nsh_common.hpp"
 #include "nsh_cplx.hpp"
+#include "nsh_stream_tile.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -58,14 +60,6 @@
 #include <utility>
 #include <vector>
 
-// Timing-only ablation hooks for tools/probe/pfft_ab.py (0 in every product build): 1 = no inverse
-// transform, 2 = no forward transform, 4 = no global loads, 8 = no phase reduction, 16 = no
-// window reads from the ring, 32 = no ring writes, 64 = no exchange writes, 128 = no product
-// writes.
-#ifndef NSH_PFFT_ABLATE
-#define NSH_PFFT_ABLATE 0
-#endif
-
 namespace {
 
 using nsh::cf;
@@ -75,19 +69,9 @@ using nsh::dft8;
 using nsh::rot;
 using nsh::virt;
 
-#ifndef NSH_PFFT_ASM_CMUL
-#define NSH_PFFT_ASM_CMUL 1
-#endif
 // a * w for the per-lane twiddles and the filter spectrum: nsh::cmul_asm (the C form cost a
 // v_xor + v_mov per product, ~4 % of the kernel)
-__device__ __forceinline__ cf cmul_tw(cf a, cf w)
-{
-#if NSH_PFFT_ASM_CMUL
-    return nsh::cmul_asm(a, w);
-#else
-    return cmulw(a, w);
-#endif
-}
+__device__ __forceinline__ cf cmul_tw(cf a, cf w) { return nsh::cmul_asm(a, w); }
 
 constexpr int M = 512;          // FFT length per phase
 constexpr int MAX_STAGES = 8;   // stages of a chain (total decimation <= 16)
@@ -135,108 +119,37 @@ __device__ __forceinline__ img_bases bases_of(cf* img, int j)
 }
 __device__ __forceinline__ img_bases bases_of(cf* img) { return bases_of(img, threadIdx.x & 63); }
 
-#ifndef NSH_PFFT_REGX2
-#define NSH_PFFT_REGX2 0
-#endif
-// Exchange 2 without LDS. Stockham's pass-2 -> pass-3 exchange moves (lane 8 a + b, register r) to
-// (lane 8 r + b, register a): it swaps lane bits 3..5 with register bits 0..2, one bit pair at a
-// time -- lane bit 5 <-> register bit 2 by v_permlane32_swap on (v[r], v[r + 4]), lane bit 4 <->
-// register bit 1 by v_permlane16_swap on (v[r], v[r + 2]), lane bit 3 <-> register bit 0 by DPP
-// row_ror:8 moves on (v[r], v[r + 1]) whose bank_mask writes only the lanes that change (lanes
-// 8..15 of each row take v[r + 1] from 8 lanes down, lanes 0..7 take v[r] from 8 lanes up).
-// 32 VALU instructions (40 as compiled) per transform instead of 8 LDS stores and 8 loads.
-// Bit-identical; measured no faster (572 vs 569 us per 2^28 inputs, profiles/r02j_pfft_lds_ab.log):
-// the VALU it adds costs what the LDS traffic it removes did. Off by default.
-__device__ __forceinline__ void swap32(cf& a, cf& b)
-{
-    const auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-    const auto y = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-    a = cf{ __uint_as_float(x[0]), __uint_as_float(y[0]) };
-    b = cf{ __uint_as_float(x[1]), __uint_as_float(y[1]) };
-}
-__device__ __forceinline__ void swap16(cf& a, cf& b)
-{
-    const auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-    const auto y = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-    a = cf{ __uint_as_float(x[0]), __uint_as_float(y[0]) };
-    b = cf{ __uint_as_float(x[1]), __uint_as_float(y[1]) };
-}
-__device__ __forceinline__ float ror8_into(float old, float src, int bank_mask_is_upper)
-{
-    return bank_mask_is_upper
-               ? __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), 0x128, 0xf, 0xc, false))
-               : __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), 0x128, 0xf, 0x3, false));
-}
-__device__ __forceinline__ void swap8(cf& a, cf& b)
-{
-    const cf na = cf{ ror8_into(a.x, b.x, 1), ror8_into(a.y, b.y, 1) };
-    const cf nb = cf{ ror8_into(b.x, a.x, 0), ror8_into(b.y, a.y, 0) };
-    a = na;
-    b = nb;
-}
-__device__ __forceinline__ void exchange2_regs(cf (&v)[8])
+// Forward 512-point transform of one phase sequence per wave, v[r] = x[lane + 64 r] (Stockham,
+// radix 8, three passes); on return v[r] = X[lane + 64 r]. The exchanges go through the wave's own
+// image ib: no workgroup barrier. t2[r] = W_64^{(lane & 7) r}, t3[r] = W_512^{lane r}. (The inverse
+// transform is conj(FFT(conj(.))), the conjugations folded into the neighbouring operations.)
+// fft512_tail: passes 2 and 3 on v[r] = the image's b1[68 r], i.e. pass 1's outputs after exchange 1
+// (k_fir_pfft2 makes that exchange across waves and scales between the loads and the tail).
+__device__ __forceinline__ void fft512_tail(cf (&v)[8], const img_bases& ib, const cf (&t2)[8], const cf (&t3)[8])
 {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) swap32(v[r], v[r + 4]);
-#pragma unroll
-    for (int r = 0; r < 8; r += 4) {
-        swap16(v[r], v[r + 2]);
-        swap16(v[r + 1], v[r + 3]);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; r += 2) swap8(v[r], v[r + 1]);
-}
-
-// Forward 512-point transforms of PW phase sequences per wave, v[i][r] = x_i[lane + 64 r]
-// (Stockham, radix 8, three passes, the PW transforms interleaved pass by pass for ILP); on
-// return v[i][r] = X_i[lane + 64 r]. Transform i exchanges through image i of the wave (ib + i IMG).
-// t2[r] = W_64^{(lane & 7) r}, t3[r] = W_512^{lane r}. The images are this wave's own: no
-// workgroup barrier. (The inverse transform is conj(FFT(conj(.))), the conjugations folded into
-// the neighbouring operations.)
-template <int PW>
-__device__ __forceinline__ void fft512_multi(cf (&v)[PW][8], const img_bases& ib, const cf (&t2)[8], const cf (&t3)[8])
-{
-#pragma unroll
-    for (int i = 0; i < PW; ++i) dft8<false>(v[i]); // pass 1 (Ns = 1) -> dst[8 j + r]
-#pragma unroll
-    for (int i = 0; i < PW; ++i)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (!(NSH_PFFT_ABLATE & 64)) ib.x1[i * IMG + r] = v[i][r];
+    for (int r = 1; r < 8; ++r) v[r] = cmul_tw(v[r], t2[r]);
+    dft8<false>(v); // pass 2 (Ns = 8) -> dst[(j >> 3) 64 + (j & 7) + 8 r]
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int i = 0; i < PW; ++i)
+    for (int r = 0; r < 8; ++r) ib.x2[8 * r + (r >= 4 ? 3 : 0)] = v[r];
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[i][r] = ib.b1[i * IMG + 68 * r];
+    for (int r = 0; r < 8; ++r) v[r] = ib.b2[72 * r];
 #pragma unroll
-    for (int i = 0; i < PW; ++i) {
+    for (int r = 1; r < 8; ++r) v[r] = cmul_tw(v[r], t3[r]);
+    dft8<false>(v); // pass 3 (Ns = 64) -> X[j + 64 r], kept in registers
+    __builtin_amdgcn_wave_barrier(); // the image is rewritten next
+}
+__device__ __forceinline__ void fft512(cf (&v)[8], const img_bases& ib, const cf (&t2)[8], const cf (&t3)[8])
+{
+    dft8<false>(v); // pass 1 (Ns = 1) -> dst[8 j + r]
 #pragma unroll
-        for (int r = 1; r < 8; ++r) v[i][r] = cmul_tw(v[i][r], t2[r]);
-        dft8<false>(v[i]); // pass 2 (Ns = 8) -> dst[(j >> 3) 64 + (j & 7) + 8 r]
-    }
-    if (NSH_PFFT_REGX2) {
+    for (int r = 0; r < 8; ++r) ib.x1[r] = v[r];
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int i = 0; i < PW; ++i) exchange2_regs(v[i]);
-    } else {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < PW; ++i)
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (!(NSH_PFFT_ABLATE & 64)) ib.x2[i * IMG + 8 * r + (r >= 4 ? 3 : 0)] = v[i][r];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < PW; ++i)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[i][r] = ib.b2[i * IMG + 72 * r];
-    }
-#pragma unroll
-    for (int i = 0; i < PW; ++i) {
-#pragma unroll
-        for (int r = 1; r < 8; ++r) v[i][r] = cmul_tw(v[i][r], t3[r]);
-        dft8<false>(v[i]); // pass 3 (Ns = 64) -> X[j + 64 r], kept in registers
-    }
-    __builtin_amdgcn_wave_barrier(); // the images are rewritten next
+    for (int r = 0; r < 8; ++r) v[r] = ib.b1[68 * r];
+    fft512_tail(v, ib, t2, t3);
 }
 
 __device__ __forceinline__ unsigned absbits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
@@ -257,6 +170,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t span_rsrc(const float2* base, 
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, bytes, 0x00020000);
 }
 
+// The stages of the chain, for frames holding inf/NaN (0 stages: the composite direct form on heq)
+struct pfft_chain {
+    const float* stap; // concatenated stage taps (device)
+    int nst;
+    int sl[MAX_STAGES];
+    int sd[MAX_STAGES];
+    int n1;            // entries of stage-1 output within a window (buffer A; buffer B follows it)
+};
+
 struct pfft_args {
     const float2* x;
     const float2* hist_in;
@@ -271,50 +193,62 @@ struct pfft_args {
     int V;
     int64_t nf;        // frames in the launch
     int64_t fpw;       // frames per workgroup
-    unsigned long long* trace; // NSH_PFFT_TRACE builds only: per-frame phase timestamps of workgroup 0
-    // the stages, for frames holding inf/NaN (0 stages: the composite direct form on heq)
-    const float* stap; // concatenated stage taps
-    int nst;
-    int sl[MAX_STAGES];
-    int sd[MAX_STAGES];
-    int n1;            // entries of stage-1 output within a window (buffer A; buffer B follows it)
+    pfft_chain ch;
 };
 
-#ifndef NSH_PFFT_TRACE
-#define NSH_PFFT_TRACE 0
-#endif
-// probe builds: s_memtime at phase k of frame f (< 64) by wave w of workgroup 0
-#define PFFT_T(k)                                                                                      \
-    do {                                                                                               \
-        if (NSH_PFFT_TRACE == 1 && blockIdx.x == 0 && f - f0 < 64 && j == 0)                            \
-            a.trace[((f - f0) * 16 + w) * 8 + (k)] = __builtin_amdgcn_s_memtime();                     \
-    } while (0)
+// The per-lane constants of wave w: the passes' twiddles and the wave's slice of F
+__device__ __forceinline__ void load_consts(cf (&t2)[8], cf (&t3)[8], cf (&fw)[8], const pfft_args& a, int w, int j)
+{
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float2 u = a.tw[8 * (((j & 7) * r) & 63)], v = a.tw[(j * r) & (M - 1)];
+        t2[r] = cf{ u.x, u.y };
+        t3[r] = cf{ v.x, v.y };
+        const float2 f = a.F[w * M + j + 64 * r];
+        fw[r] = cf{ f.x, f.y };
+    }
+}
+// Re-defines them (empty asm), once per frame: otherwise the compiler hoists the swizzled/negated
+// copies that cmulw's operand modifiers give for free, i.e. holds every twiddle twice (the kernels
+// have 128 VGPRs at 16 waves per CU).
+__device__ __forceinline__ void redefine_consts(cf (&t2)[8], cf (&t3)[8], cf (&fw)[8])
+{
+#pragma unroll
+    for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(fw[r]));
+#pragma unroll
+    for (int r = 1; r < 8; ++r) asm volatile("" : "+v"(t2[r]), "+v"(t3[r]));
+}
 
-// Workgroup shape: P phases, PW per wave, NT = 64 P / PW threads. A frame's V new rows are P V / 2
-// 16-B loads, i.e. ceil(V PW / 128) <= 4 PW per thread (V <= 512).
-template <int P, int PW>
-struct pshape {
-    static constexpr int NT = 64 * P / PW;
-    static constexpr int WAVES = P / PW;
-    static constexpr int PRE = 4 * PW;
-    static constexpr int RSTEP = 128 / PW; // ring rows between a thread's consecutive slots
+// A frame's scale from wm, the largest magnitude bits in its window: the input times 2^ks lies in
+// [1, 2), the outputs are multiplied by 2^-ks. bad: the window holds inf or NaN.
+// A window whose largest magnitude lies in [2^-40, 2^41) -- every stream but extreme ones -- is not
+// scaled: a power-of-two scale is exact, so this changes no output bit, and none of such a frame's
+// intermediates leaves fp32's normal range (saves 8 packed multiplies).
+__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }
+struct fscale {
+    bool bad, scale;
+    int ks;
+    float sc; // 2^ks
 };
+__device__ __forceinline__ fscale frame_scale(unsigned wm)
+{
+    fscale s;
+    s.bad = wm >= 0x7f800000u;
+    int ks = 127 - (int)(wm >> 23); // max * 2^ks in [1, 2)
+    ks = ks > 126 ? 126 : (ks < -126 ? -126 : ks);
+    s.scale = ks < -40 || ks > 40;
+    s.ks = s.scale ? ks : 0;
+    s.sc = pow2f(s.ks);
+    return s;
+}
 
-#ifndef NSH_PFFT_RINGORDER
-#define NSH_PFFT_RINGORDER 1 // the window transformed in ring order (rotated), the rotation undone at the output
-#endif
-#ifndef NSH_PFFT_SPLIT_WIN
-#define NSH_PFFT_SPLIT_WIN 1
-#endif
-#ifndef NSH_PFFT_SPLIT_READS
-#define NSH_PFFT_SPLIT_READS 1
-#endif
-#ifndef NSH_PFFT_SCALE_ALWAYS
-#define NSH_PFFT_SCALE_ALWAYS 0
-#endif
-#ifndef NSH_PFFT_ROWPERM
-#define NSH_PFFT_ROWPERM 1
-#endif
+// Workgroup shape of the ring form: P phases, one per wave (two per wave -- half the product and
+// reduction LDS traffic, two independent transforms per wave -- measured 650 vs 600 us per 2^28 inputs:
+// 16 waves cover LDS latency better, profiles/r02i_ab_pfft_pw.log). A frame's V new rows are P V / 2
+// 16-B loads, i.e. ceil(V / 128) <= PRE per thread (V <= 512).
+constexpr int PRE = 4;
+constexpr int RSTEP = 128; // ring rows between a thread's consecutive slots
+
 // The 16-B slot (2 samples, phases 2m and 2m + 1 of one row) that thread t moves: a permutation of
 // the slots within each wave's 1 KiB (loads stay one contiguous 1 KiB per wave-instruction) such
 // that each 16-lane store group covers rows whose swizzles differ in parity -- P = 16: rows b and
@@ -324,54 +258,49 @@ struct pshape {
 template <int P>
 __device__ __forceinline__ int row_slot(int t)
 {
-    if (!NSH_PFFT_ROWPERM) return t;
     const int l = t & 63, g = l >> 4;
     if (P == 16) return (t & ~63) + (4 * (g >> 1) + (g & 1) + 2 * ((l >> 3) & 1)) * 8 + (l & 7);
     const int h = (l >> 2) & 3;
     return (t & ~63) + (8 * (g >> 1) + 2 * (g & 1) + (h & 1) + 4 * (h >> 1)) * 4 + (l & 3);
 }
 
-template <int P, int PW>
-__device__ __forceinline__ void load_rows(float4 (&pre)[4 * PW], const pfft_args& a, int64_t n_in, int64_t fn)
+template <int P>
+__device__ __forceinline__ void load_rows(float4 (&pre)[PRE], const pfft_args& a, int64_t n_in, int64_t fn)
 {
-    using S = pshape<P, PW>;
     // window fn's new rows = x[P fn V, P (fn + 1) V); slots past them read 0
     const int64_t b = (int64_t)P * fn * a.V;
     const __amdgpu_buffer_rsrc_t r = span_rsrc(a.x + b, n_in - b, (int64_t)P * a.V);
 #pragma unroll
-    for (int k = 0; k < S::PRE; ++k) pre[k] = nsh::buf_load_f4(r, (row_slot<P>(threadIdx.x) + S::NT * k) * 16);
+    for (int k = 0; k < PRE; ++k) pre[k] = nsh::buf_load_f4(r, (row_slot<P>(threadIdx.x) + 64 * P * k) * 16);
 }
 
 // write the prefetched rows of window fn into the ring; returns this thread's max magnitude bits.
-// Slot k of thread t holds samples 2 i, 2 i + 1, i = u + NT k, u = row_slot(t): rows (2 u) / P +
+// Slot k of thread t holds samples 2 i, 2 i + 1, i = u + 64 P k, u = row_slot(t): rows (2 u) / P +
 // RSTEP k, phases (2 u) % P and + 1 -- one swizzle for every k (RSTEP k / (32 / P) is a multiple
 // of P), so each ring entry is one of two bases plus RSTEP P k, modulo the ring.
-template <int P, int PW>
-__device__ __forceinline__ unsigned store_rows(const float4 (&pre)[4 * PW], cf* __restrict__ ring,
-                                               const pfft_args& a, int64_t fn)
+template <int P>
+__device__ __forceinline__ unsigned store_rows(const float4 (&pre)[PRE], cf* __restrict__ ring, const pfft_args& a, int64_t fn)
 {
-    using S = pshape<P, PW>;
     const int items = P * a.V / 2;
     const int t = row_slot<P>(threadIdx.x);
     const int s0 = (int)((fn * a.V + a.Q + (2 * t) / P) & (M - 1)), ph = (2 * t) % P;
     const int ea = ring_at<P>(s0, ph), eb = ring_at<P>(s0, ph + 1);
     unsigned m = 0;
 #pragma unroll
-    for (int k = 0; k < S::PRE; ++k) {
-        if (t + S::NT * k < items) {
-            ring[(ea + S::RSTEP * P * k) & (M * P - 1)] = cf{ pre[k].x, pre[k].y };
-            ring[(eb + S::RSTEP * P * k) & (M * P - 1)] = cf{ pre[k].z, pre[k].w };
+    for (int k = 0; k < PRE; ++k) {
+        if (t + 64 * P * k < items) {
+            ring[(ea + RSTEP * P * k) & (M * P - 1)] = cf{ pre[k].x, pre[k].y };
+            ring[(eb + RSTEP * P * k) & (M * P - 1)] = cf{ pre[k].z, pre[k].w };
             m = max(m, maxbits4(pre[k]));
         }
     }
     return m;
 }
 
-template <int P, int PW>
-__global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
+template <int P>
+__global__ __launch_bounds__(64 * P, 1) void k_fir_pfft(pfft_args a)
 {
-    using S = pshape<P, PW>;
-    constexpr int NT = S::NT, WAVES = S::WAVES;
+    constexpr int NT = 64 * P, WAVES = P;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     cf* ring = reinterpret_cast<cf*>(lds);   // M * P
     cf* imgs = ring + M * P;                  // P * IMG
@@ -385,24 +314,13 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
     if (f0 >= f1) return; // whole workgroup
     const int64_t n_in = a.n_out * P;
     const int L = a.L, Q = a.Q, V = a.V;
-    const img_bases ib = bases_of(imgs + w * PW * IMG); // the wave's PW images; products in the first
-    if (NSH_PFFT_TRACE == 2 && tid == 0) a.trace[2 * blockIdx.x] = __builtin_amdgcn_s_memtime(); // probe: workgroup span
+    const img_bases ib = bases_of(imgs + w * IMG); // the wave's image
 
     if (a.hist_out && blockIdx.x == gridDim.x - 1) // the next call's history: the L-1 samples before x[n_in]
-        for (int k = tid; k < L - 1; k += NT) a.hist_out[k] = virt(a.x, a.hist_in, n_in - (L - 1) + k, n_in, L);
+        nsh::store_history<NT>(a.x, a.hist_in, a.hist_out, n_in, L, tid);
 
-    cf t2[8], t3[8], fw[PW][8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const float2 u = a.tw[8 * (((j & 7) * r) & 63)], v = a.tw[(j * r) & (M - 1)];
-        t2[r] = cf{ u.x, u.y };
-        t3[r] = cf{ v.x, v.y };
-#pragma unroll
-        for (int i = 0; i < PW; ++i) {
-            const float2 f = a.F[(w * PW + i) * M + j + 64 * r];
-            fw[i][r] = cf{ f.x, f.y };
-        }
-    }
+    cf t2[8], t3[8], fw[8];
+    load_consts(t2, t3, fw, a, w, j);
 
     // first window: rows [f0 V, f0 V + M), history-aware. Its maximum in two parts, the new rows in
     // frame f0's slot and the Q overlap rows before them in the other one (as if frame f0 - 1 had left
@@ -425,89 +343,50 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
         mx[(f0 & 1) * WAVES + w] = m;
         mx[((f0 + 1) & 1) * WAVES + w] = mo;
     }
-    float4 pre[S::PRE];
-    load_rows<P, PW>(pre, a, n_in, f0 + 1);
+    float4 pre[PRE];
+    load_rows<P>(pre, a, n_in, f0 + 1);
     nsh::lds_barrier();
 
     for (int64_t f = f0; f < f1; ++f) {
-        PFFT_T(0);
         // The next window's rows (consumed in this frame's phase B) are requested here, at the top
         // of the transform phase: the CU's texture path moves 64 B/clk, so the 50 KB of a frame's
         // new rows take ~800 cycles to issue and ~800 to return -- issued in phase B they held
         // every wave there; here they overlap the transforms.
-        if (f > f0 && !(NSH_PFFT_ABLATE & 4)) load_rows<P, PW>(pre, a, n_in, f + 1 < f1 ? f + 1 : a.nf + 1);
-        // Re-define the per-lane constants each frame (empty asm): otherwise the compiler hoists
-        // the swizzled/negated copies that cmulw's operand modifiers give for free, i.e. holds
-        // every twiddle twice (the kernel has 128 VGPRs at 16 waves per CU).
-#pragma unroll
-        for (int i = 0; i < PW; ++i)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(fw[i][r]));
-#pragma unroll
-        for (int r = 1; r < 8; ++r) asm volatile("" : "+v"(t2[r]), "+v"(t3[r]));
+        if (f > f0) load_rows<P>(pre, a, n_in, f + 1 < f1 ? f + 1 : a.nf + 1);
+        redefine_consts(t2, t3, fw);
         // the window's largest magnitude: this frame's new rows and the previous frame's (which
         // hold the overlap; before the first window, the overlap rows alone)
         const unsigned wm = nsh::wave_umax(j < 2 * WAVES ? mx[j] : 0u); // one LDS read, DPP max
-        const bool bad = wm >= 0x7f800000u; // inf or NaN in the window
-        int ks = 127 - (int)(wm >> 23);      // max * 2^ks in [1, 2)
-        ks = ks > 126 ? 126 : (ks < -126 ? -126 : ks);
-        // A window whose largest magnitude lies in [2^-40, 2^41) -- every stream but extreme ones --
-        // is not scaled: a power-of-two scale is exact, so this changes no output bit, and none of
-        // such a frame's intermediates leaves fp32's normal range (saves 8 packed multiplies).
-        const bool scale = NSH_PFFT_SCALE_ALWAYS || ks < -40 || ks > 40;
-        if (!scale) ks = 0;
-        const float sc = __uint_as_float((unsigned)(ks + 127) << 23);
-        const float usc = __uint_as_float((unsigned)(127 - ks) << 23);
+        const fscale fs = frame_scale(wm);
+        const bool bad = fs.bad, scale = fs.scale;
+        const float sc = fs.sc, usc = pow2f(-fs.ks);
         const int64_t rowf = f * V;
         if (!bad) {
-            cf v[PW][8];
-#if NSH_PFFT_RINGORDER
+            cf v[8];
             // The window in ring order: slot t = (rowf + q) mod M holds window row q, i.e. the
             // sequence read is the window rotated by s = rowf mod M. Its transform is the window's
             // times W^{s k} for every phase alike, so the inverse yields c rotated by s, which the
             // output stores undo (q = (t - s) mod M). Slots j + 64 r share one swizzle, so the eight
             // reads are one per-lane base plus immediate offsets -- no per-frame address arithmetic
-            // (the rotation-free form spent ~30 VALU per wave and frame on it).
-#pragma unroll
-            for (int i = 0; i < PW; ++i) {
-                const cf* rb = ring + ring_at<P>(j, w * PW + i);
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    v[i][r] = (NSH_PFFT_ABLATE & 16) ? cf{ sc, (float)r } : rb[64 * P * r];
-                    // single ds_read_b64 each: paired (ds_read2st64_b64) they are served in 16-lane
-                    // groups, where lanes 2 t and 2 t + 1 share a swizzle -- 2-way conflicts on every
-                    // window read (2.7 M conflict cycles per 2^25 inputs, r04zm); in the 32-lane
-                    // groups of single reads the two rows of a pair sit 16 bank pairs apart
-                    if (NSH_PFFT_SPLIT_WIN) asm volatile("" ::: "memory");
-                }
-            }
-#else
-            // rows rowf + j + 64 r share one swizzle (64 r moves s / (32 / P) by a multiple of P)
-            const int sr = (int)((rowf + j) & (M - 1));
-#pragma unroll
-            for (int i = 0; i < PW; ++i) {
-                const int e0 = ring_at<P>(sr, w * PW + i);
-#pragma unroll
-                for (int r = 0; r < 8; ++r)
-                    v[i][r] = (NSH_PFFT_ABLATE & 16) ? cf{ sc, (float)r } : ring[(e0 + 64 * P * r) & (M * P - 1)];
-            }
-#endif
-            if (scale) { // wave-uniform branch
-#pragma unroll
-                for (int i = 0; i < PW; ++i)
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[i][r] *= sc;
-            }
-            if (!(NSH_PFFT_ABLATE & 2)) fft512_multi<PW>(v, ib, t2, t3);
-            // this wave's share of the phase sum, in a fixed order (deterministic)
+            // (a rotation-free read spent ~30 VALU per wave and frame on it).
+            const cf* rb = ring + ring_at<P>(j, w);
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
-                cf pr = cmul_tw(v[0][r], fw[0][r]);
-#pragma unroll
-                for (int i = 1; i < PW; ++i) pr += cmul_tw(v[i][r], fw[i][r]);
-                if (!(NSH_PFFT_ABLATE & 128)) ib.n[64 * r] = pr;
+                v[r] = rb[64 * P * r];
+                // single ds_read_b64 each: paired (ds_read2st64_b64) they are served in 16-lane
+                // groups, where lanes 2 t and 2 t + 1 share a swizzle -- 2-way conflicts on every
+                // window read (2.7 M conflict cycles per 2^25 inputs, r04zm); in the 32-lane
+                // groups of single reads the two rows of a pair sit 16 bank pairs apart
+                asm volatile("" ::: "memory");
             }
-        } else if (a.nst < 2) {
+            if (scale) { // wave-uniform branch
+#pragma unroll
+                for (int r = 0; r < 8; ++r) v[r] *= sc;
+            }
+            fft512(v, ib, t2, t3);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) ib.n[64 * r] = cmul_tw(v[r], fw[r]); // times F_p, into the wave's image
+        } else if (a.ch.nst < 2) {
             // one stage: the fp32 direct form on its taps (heq = h): y[j] = sum_n heq[n] u[P q - n], q = Q + t
             for (int t = tid; t < V; t += NT) {
                 const int q = Q + t;
@@ -527,12 +406,14 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
             // between two buffers in the wave images (free now: the barrier waits for the previous
             // frame's inverse wave); values near the window start use a truncated history and are
             // never read by a final output.
+            // (Written out here and in k_fir_pfft2: as one function over a window reader u(tau),
+            // k_fir_pfft2 took one more spilled SGPR and ran 1.3-2.5 % slower, profiles/pfft_refactor_ab.log.)
             nsh::lds_barrier();
-            cf* buf[2] = { imgs, imgs + a.n1 };
-            const float* hs = a.stap;
+            cf* buf[2] = { imgs, imgs + a.ch.n1 };
+            const float* hs = a.ch.stap;
             int n_prev = P * M;
-            for (int st = 0; st < a.nst; ++st) {
-                const int Ds = a.sd[st], Ls = a.sl[st];
+            for (int st = 0; st < a.ch.nst; ++st) {
+                const int Ds = a.ch.sd[st], Ls = a.ch.sl[st];
                 const int n_cur = (n_prev - 1) / Ds + 1;
                 const cf* src = buf[(st + 1) & 1];
                 cf* dst = buf[st & 1];
@@ -550,13 +431,11 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
                 n_prev = n_cur;
                 nsh::lds_barrier();
             }
-            const cf* last = buf[(a.nst - 1) & 1]; // y[m] at local m = Q + t
+            const cf* last = buf[(a.ch.nst - 1) & 1]; // y[m] at local m = Q + t
             for (int t = tid; t < V; t += NT)
                 if (rowf + t < a.n_out) a.out[rowf + t] = make_float2(last[Q + t].x, last[Q + t].y);
         }
-        PFFT_T(1);
         nsh::lds_barrier(); // B1: window f read, images hold the per-phase products
-        PFFT_T(2);
         if (!bad) {
 #pragma unroll
             for (int k = tid; k < M; k += NT) {
@@ -566,55 +445,39 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
                 cf pv[WAVES];
 #pragma unroll
                 for (int u = 0; u < WAVES; ++u) {
-                    pv[u] = src[u * PW * IMG];
-                    if (NSH_PFFT_SPLIT_READS) asm volatile("" ::: "memory");
+                    pv[u] = src[u * IMG];
+                    asm volatile("" ::: "memory");
                 }
                 cf z = pv[0];
 #pragma unroll
-                for (int u = 1; u < ((NSH_PFFT_ABLATE & 8) ? 1 : WAVES); ++u) z += pv[u];
+                for (int u = 1; u < WAVES; ++u) z += pv[u];
                 zb[k] = cf{ z.x, -z.y }; // conj: the inverse runs as a forward transform
             }
         }
-        PFFT_T(6);
         if (f + 1 < f1) {
-            unsigned mn = nsh::wave_umax(store_rows<P, PW>(pre, ring, a, f + 1));
+            unsigned mn = nsh::wave_umax(store_rows<P>(pre, ring, a, f + 1));
             if (j == 0) mx[((f + 1) & 1) * WAVES + w] = mn;
-            PFFT_T(7);
         }
-        PFFT_T(3);
         nsh::lds_barrier(); // B2: Z and window f+1 complete
-        PFFT_T(4);
         // the inverse transform goes to one of waves 0..3 (one per SIMD, the oldest and so the
         // first in each SIMD's issue arbitration), rotating over the four SIMDs
-        if (!(NSH_PFFT_ABLATE & 1) && !bad && w == (int)(f & 3)) {
-            cf v[1][8];
+        if (!bad && w == (int)(f & 3)) {
+            cf v[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) v[0][r] = zb[j + 64 * r];
-            fft512_multi<1>(v, ib, t2, t3);
+            for (int r = 0; r < 8; ++r) v[r] = zb[j + 64 * r];
+            fft512(v, ib, t2, t3);
             const __amdgpu_buffer_rsrc_t ro = span_rsrc(a.out + rowf, a.n_out - rowf, V);
             const cf us = cf{ usc, -usc }; // 2^-k and the output conjugation
-#if NSH_PFFT_RINGORDER
             // slot t = j + 64 r holds output row q = (t - s) mod M (the window was read in ring order)
             int t0 = j - (int)(rowf & (M - 1));
             asm volatile("" : "+v"(t0)); // computed here, not hoisted
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int q = (t0 + 64 * r) & (M - 1);
-                if (q >= Q) nsh::buf_store_f2(ro, (q - Q) * 8, v[0][r] * us);
+                if (q >= Q) nsh::buf_store_f2(ro, (q - Q) * 8, v[r] * us);
             }
-#else
-            int ob = (j - Q) * 8;
-            asm volatile("" : "+v"(ob)); // computed here, not hoisted (8 offsets would spill)
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (j + 64 * r >= Q) nsh::buf_store_f2(ro, ob + 512 * r, v[0][r] * us);
-#endif
-            PFFT_T(5);
         }
     }
-    if (NSH_PFFT_TRACE == 2 && j == 0) // probe: the last wave to leave sets the workgroup's end
-        __hip_atomic_fetch_max(&a.trace[2 * blockIdx.x + 1], (unsigned long long)__builtin_amdgcn_s_memtime(),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- k_fir_pfft2: the P = 16 frame without a ring, phase images double-buffered (round 5) ----
@@ -651,44 +514,25 @@ __global__ __launch_bounds__(64 * P / PW, 1) void k_fir_pfft(pfft_args a)
 // reading its window from HBM.
 constexpr int IMG2 = 571; // odd: a 16-lane group's exchange-1 stores (16 phases, one position) hit 16 bank pairs
 
-// timing-only ablation hook for tools/probe (0 in every product build): 2 = no row loads
-#ifndef NSH_PFFT2_ABLATE
-#define NSH_PFFT2_ABLATE 0
-#endif
 // The inverse of a frame runs on wave INV_BASE + (frame & 3), one per SIMD. Waves 4..7 (the
 // second-oldest quartet: the phase sum's waves 0..3 start their transforms without it, and waves
 // 4..7 arrive ~1.8k cycles early at B2 in the phase trace) measured 0.6-0.8 % faster than 0..3 in four two-library
 // A/Bs (r05zq; r05zo 2-3 %); 8..11 and 12..15 are 5-18 % slower (r05zp); after the wave's row loads
 // instead of before them, level or slower (r05zo).
-#ifndef NSH_PFFT2_REGX2
-#define NSH_PFFT2_REGX2 0
-#endif
-#ifndef NSH_PFFT2_INV_BASE
-#define NSH_PFFT2_INV_BASE 4
-#endif
-// Probe (round 6): waves w >= NSH_PFFT2_LATE_FROM issue the next frame's row loads after their
-// products instead of after B1 (into the same registers: a second set spills). The phase
-// trace puts the youngest waves' load issue ~2.7k cycles after B1, behind the older waves' loads
-// in the CU's vector-memory queue, with their transforms waiting behind it; loading late, they
-// transform first and meet an idle queue while the older waves run the phase sum. Measured 12-17 %
-// slower (waves 4..15 / 8..15 / 12..15 late: 615-620 / 637-641 / 614 vs 542-549 us per 2^28
+constexpr int INV_BASE = 4;
+// The next frame's row loads are issued after B1 by every wave. Issued after their products by the
+// youngest waves instead (which then transform first and meet an idle vector-memory queue) measured
+// 12-17 % slower (waves 4..15 / 8..15 / 12..15 late: 615-620 / 637-641 / 614 vs 542-549 us per 2^28
 // inputs, bit-identical, both orders, profiles/r06w_pfft2_late_loads_ab.log): the data's latency,
-// exposed before pass 1, costs more than the issue queue did. 16 = off (the product build).
-#ifndef NSH_PFFT2_LATE_FROM
-#define NSH_PFFT2_LATE_FROM 16
-#endif
+// exposed before pass 1, costs more than the issue queue did.
 // Row-load cache policy: a frame's rows V .. M - 1 (V >= 384 for Q <= 128) are the next frame's
 // first rows, read again one frame later (mostly L2 hits); rows below V are read for the last
 // time. Load 3 holds rows 384 .. 511 and keeps the default policy; loads 0..2 stream
 // (nontemporal), so they do not push the overlap rows out of L2 before they are read again:
 // 8.72 vs 9.00 HBM B per input, time level or 0.3 % faster (r05zi); nontemporal on all four
 // loses the overlap hits (10.44 B, 2 % slower).
-#ifndef NSH_PFFT2_LD_AUX
-#define NSH_PFFT2_LD_AUX 2 // loads 0..2
-#endif
-#ifndef NSH_PFFT2_LD_AUX3
-#define NSH_PFFT2_LD_AUX3 0 // load 3
-#endif
+constexpr int LD_AUX = 2;  // loads 0..2
+constexpr int LD_AUX3 = 0; // load 3
 
 // Frame f's window, x[P (f V - Q) + i], i < P M, in 16-B loads: lane l = 32 h + q of wave w loads
 // phases 2 m, 2 m + 1 (m = q & 7) of rows jp + 64 (2 k + h), k = 0..3, jp = 4 w + g,
@@ -717,8 +561,8 @@ __device__ __forceinline__ void load_frame(cf (&v)[8], const pfft_args& a, int64
         nsh::buf_f4 t[4];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            t[k] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (e0 + 128 * P * k) * 8, 0, NSH_PFFT2_LD_AUX));
-        t[3] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (e0 + 384 * P) * 8, 0, NSH_PFFT2_LD_AUX3));
+            t[k] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (e0 + 128 * P * k) * 8, 0, LD_AUX));
+        t[3] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (e0 + 384 * P) * 8, 0, LD_AUX3));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             v[2 * k] = cf{ t[k].x, t[k].y };
@@ -744,16 +588,10 @@ __device__ __forceinline__ void load_rows16(nsh::buf_f4 (&x)[4], const pfft_args
 {
     const int64_t b = (int64_t)P * (f * a.V - a.Q);
     const __amdgpu_buffer_rsrc_t r = span_rsrc(a.x + b, live ? n_in - b : 0, (int64_t)P * M);
-#if NSH_PFFT2_ABLATE & 2 // timing only: no row loads
-    (void)r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = nsh::buf_f4{ (float)k, 1.f, 2.f, (float)e0 };
-#else
 #pragma unroll
     for (int k = 0; k < 3; ++k) // one address VGPR: the load's distance in the scalar offset
-        x[k] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, e0 * 8, 1024 * P * k, NSH_PFFT2_LD_AUX));
-    x[3] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, e0 * 8, 1024 * P * 3, NSH_PFFT2_LD_AUX3));
-#endif
+        x[k] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, e0 * 8, 1024 * P * k, LD_AUX));
+    x[3] = __builtin_bit_cast(nsh::buf_f4, __builtin_amdgcn_raw_buffer_load_b128(r, e0 * 8, 1024 * P * 3, LD_AUX3));
 }
 __device__ __forceinline__ void unpack_rows(cf (&v)[8], const nsh::buf_f4 (&x)[4])
 {
@@ -811,17 +649,10 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
     const int e1off = pp * IMG2 + 8 * jp + (jp >> 1);
 
     if (a.hist_out && blockIdx.x == gridDim.x - 1) // the next call's history: the L-1 samples before x[n_in]
-        for (int k = tid; k < L - 1; k += NT) a.hist_out[k] = virt(a.x, a.hist_in, n_in - (L - 1) + k, n_in, L);
+        nsh::store_history<NT>(a.x, a.hist_in, a.hist_out, n_in, L, tid);
 
     cf t2[8], t3[8], fw[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const float2 u = a.tw[8 * (((j & 7) * r) & 63)], v = a.tw[(j * r) & (M - 1)];
-        t2[r] = cf{ u.x, u.y };
-        t3[r] = cf{ v.x, v.y };
-        const float2 fv = a.F[w * M + j + 64 * r];
-        fw[r] = cf{ fv.x, fv.y };
-    }
+    load_consts(t2, t3, fw, a, w, j);
 
     // the inverse of frame fi (conj(Z) in zb[fi & 1]) by this wave, its exchanges in iimg
     // (the lane's addresses of the inverse and the phase sum are recomputed from an opaque copy of
@@ -829,19 +660,19 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
     auto inverse = [&](int64_t fi, int ksi) {
         int jj = j;
         asm volatile("" : "+v"(jj));
-        cf v[1][8];
+        cf v[8];
         const cf* z = zb + (int)(fi & 1) * M + jj;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[0][r] = z[64 * r];
-        fft512_multi<1>(v, bases_of(iimg, jj), t2, t3);
+        for (int r = 0; r < 8; ++r) v[r] = z[64 * r];
+        fft512(v, bases_of(iimg, jj), t2, t3);
         const int64_t rowi = fi * V;
         const __amdgpu_buffer_rsrc_t ro = span_rsrc(a.out + rowi, a.n_out - rowi, V);
-        const float us = __uint_as_float((unsigned)(127 - ksi) << 23);
+        const float us = pow2f(-ksi);
         const cf u2 = cf{ us, -us }; // 2^-k and the output conjugation
         const int ob = (jj - Q) * 8;
 #pragma unroll
         for (int r = 0; r < 8; ++r)
-            if (jj + 64 * r >= Q) nsh::buf_store_f2(ro, ob + 512 * r, v[0][r] * u2);
+            if (jj + 64 * r >= Q) nsh::buf_store_f2(ro, ob + 512 * r, v[r] * u2);
     };
     // the phase sum of frame fi (products in set fi & 1) into zb[fi & 1], by waves 0..7, in a fixed
     // order (deterministic). (The oldest waves: the youngest, last in issue arbitration, wait longest
@@ -865,7 +696,7 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
         zb[(int)(fi & 1) * M + k] = cf{ zz.x, -zz.y }; // conj: the inverse runs as a forward transform
     };
 
-    auto inv_wave = [](int64_t fi) { return (int)(fi & 3) + NSH_PFFT2_INV_BASE; };
+    auto inv_wave = [](int64_t fi) { return (int)(fi & 3) + INV_BASE; };
     // v: the next frame's rows, loaded during the current frame's phase A, then its pass 1
     cf v[8];
     auto pass1_of = [&](int64_t fn) { // rows of frame fn in v -> its wave max in mx[fn & 1], pass 1 in v
@@ -883,26 +714,18 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
     for (int64_t f = f0; f < f1; ++f) {
         const int s = (int)(f & 1);
         cf* cur = sets + s * SET;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(fw[r]));
-#pragma unroll
-        for (int r = 1; r < 8; ++r) asm volatile("" : "+v"(t2[r]), "+v"(t3[r]));
-        PFFT_T(0);
+        redefine_consts(t2, t3, fw);
         nsh::buf_f4 nx[4]; // the next frame's rows, requested after B1
         // A0: frame f's pass-1 outputs (computed at the end of the previous phase A) into set s
 #pragma unroll
         for (int r = 0; r < 8; ++r) cur[e1off + r] = v[r];
-        PFFT_T(1);
         nsh::lds_barrier(); // B1: exchange 1 of frame f complete
-        PFFT_T(2);
 
         const unsigned wm = nsh::wave_umax(j < P ? mx[s * P + j] : 0u);
-        const bool bad = wm >= 0x7f800000u; // inf or NaN in the window
-        int ks = 127 - (int)(wm >> 23);
-        ks = ks > 126 ? 126 : (ks < -126 ? -126 : ks);
-        const bool scale = ks < -40 || ks > 40;
-        if (!scale) ks = 0;
-        const float sc = __uint_as_float((unsigned)(ks + 127) << 23);
+        const fscale fs = frame_scale(wm);
+        const bool bad = fs.bad, scale = fs.scale;
+        const int ks = fs.ks;
+        const float sc = fs.sc;
         // pass 1 unscaled is safe for maxima in [2^-100, 2^124); outside it, redo pass 1 on scaled rows
         const bool redo = !bad && (wm >= (251u << 23) || (wm != 0u && wm < (27u << 23)));
         if (redo) { // workgroup-uniform
@@ -923,12 +746,7 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
         // of frame f - 1 (waves 0..7; set s ^ 1 is rewritten only by frame f + 1's pass 1, after B2),
         // the next frame's pass 1
         if (inv2 && w == inv_wave(f - 2)) inverse(f - 2, ks2);
-#if NSH_PFFT2_LATE_FROM < 16
-        const bool late = w >= NSH_PFFT2_LATE_FROM; // wave-uniform
-        if (!late)
-#endif
-            load_rows16<P>(nx, a, n_in, f + 1, f + 1 < f1, e0);
-        PFFT_T(3);
+        load_rows16<P>(nx, a, n_in, f + 1, f + 1 < f1, e0);
         const int64_t rowf = f * V;
         if (!bad) {
             const img_bases ib = bases_of(cur + w * IMG2);
@@ -939,26 +757,10 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
 #pragma unroll
                 for (int r = 0; r < 8; ++r) u[r] *= sc;
             }
-#pragma unroll
-            for (int r = 1; r < 8; ++r) u[r] = cmul_tw(u[r], t2[r]);
-            dft8<false>(u); // pass 2 -> dst[(j >> 3) 64 + (j & 7) + 8 r]
-#if NSH_PFFT2_REGX2
-            exchange2_regs(u); // probe: exchange 2 by lane swaps instead of the wave's image
-#else
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) ib.x2[8 * r + (r >= 4 ? 3 : 0)] = u[r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) u[r] = ib.b2[72 * r];
-#endif
-#pragma unroll
-            for (int r = 1; r < 8; ++r) u[r] = cmul_tw(u[r], t3[r]);
-            dft8<false>(u); // pass 3 -> X[j + 64 r]
-            __builtin_amdgcn_wave_barrier();
+            fft512_tail(u, ib, t2, t3);
 #pragma unroll
             for (int r = 0; r < 8; ++r) ib.n[64 * r] = cmul_tw(u[r], fw[r]);
-        } else if (a.nst < 2) {
+        } else if (a.ch.nst < 2) {
             // one stage: the fp32 direct form on its taps (heq = h) over the window in HBM
             const int64_t wb = (int64_t)P * (rowf - Q);
             for (int t = tid; t < V; t += NT) {
@@ -974,11 +776,11 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
             // the staged chain, stage by stage in the fp32 direct form (as k_fir_pfft), its window
             // read from HBM, stage outputs ping-ponging between two buffers in set s
             const int64_t wb = (int64_t)P * (rowf - Q);
-            cf* buf[2] = { cur, cur + a.n1 };
-            const float* hs = a.stap;
+            cf* buf[2] = { cur, cur + a.ch.n1 };
+            const float* hs = a.ch.stap;
             int n_prev = P * M;
-            for (int st = 0; st < a.nst; ++st) {
-                const int Ds = a.sd[st], Ls = a.sl[st];
+            for (int st = 0; st < a.ch.nst; ++st) {
+                const int Ds = a.ch.sd[st], Ls = a.ch.sl[st];
                 const int n_cur = (n_prev - 1) / Ds + 1;
                 const cf* src = buf[(st + 1) & 1];
                 cf* dst = buf[st & 1];
@@ -1002,22 +804,16 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
                 n_prev = n_cur;
                 nsh::lds_barrier();
             }
-            const cf* last = buf[(a.nst - 1) & 1]; // y[m] at local m = Q + t
+            const cf* last = buf[(a.ch.nst - 1) & 1]; // y[m] at local m = Q + t
             for (int t = tid; t < V; t += NT)
                 if (rowf + t < a.n_out) a.out[rowf + t] = make_float2(last[Q + t].x, last[Q + t].y);
         }
-        PFFT_T(4);
-#if NSH_PFFT2_LATE_FROM < 16
-        if (late) load_rows16<P>(nx, a, n_in, f + 1, f + 1 < f1, e0); // the same registers, loaded late
-#endif
         if (sum1 && w < P / 2) phase_sum(f - 1);
         if (f + 1 < f1) {
             unpack_rows(v, nx);
             pass1_of(f + 1);
         }
-        PFFT_T(5);
         nsh::lds_barrier(); // B2: the products of frame f and Z of frame f - 1 complete
-        PFFT_T(6);
         inv2 = sum1;
         ks2 = ks1;
         sum1 = !bad;
@@ -1034,15 +830,6 @@ __global__ __launch_bounds__(64 * P, 1) void k_fir_pfft2(pfft_args a)
 
 using nsh::set_lds_attr;
 
-// Phases per wave. Two per wave (8 waves at P = 16, half the product and reduction LDS traffic,
-// two independent transforms per wave) measured 650 vs 600 us per 2^28 inputs against one per
-// wave (16 waves: more waves per SIMD to cover LDS latency; profiles/r02i_ab_pfft_pw.log).
-#ifndef NSH_PFFT_PW16
-#define NSH_PFFT_PW16 1
-#endif
-constexpr int PW16 = NSH_PFFT_PW16;
-constexpr int PW8 = 1;
-
 template <int P>
 constexpr int lds_bytes()
 {
@@ -1058,9 +845,31 @@ static_assert(lds_bytes2<16>() <= 160 * 1024, "k_fir_pfft2's LDS");
 
 // The C5 (P = 16) form: 2 = k_fir_pfft2 (round 5, default: 2.2-2.5 % faster, r05y), 1 = k_fir_pfft (environment
 // NSH_PFFT_FORM at plan creation, for one-process A/B and the tests of both)
-#ifndef NSH_PFFT_FORM16
-#define NSH_PFFT_FORM16 2
-#endif
+constexpr int FORM16 = 2;
+
+// The kernel of a plan (D phases; form as above, 1 at D = 8), its dynamic LDS, threads and name. The
+// ring form's name keeps its second argument, the phases per wave: 1, the only form since round 2.
+struct pfft_form {
+    void (*kernel)(pfft_args);
+    int lds;
+    int nt;
+    const char* name;
+};
+pfft_form form_of(int D, int form)
+{
+    if (form == 2) return { k_fir_pfft2<16>, lds_bytes2<16>(), 64 * 16, "k_fir_pfft2<16>" };
+    if (D == 16) return { k_fir_pfft<16>, lds_bytes<16>(), 64 * 16, "k_fir_pfft<16,1>" };
+    return { k_fir_pfft<8>, lds_bytes<8>(), 64 * 8, "k_fir_pfft<8,1>" };
+}
+
+// a host table to a fresh allocation on the current device; nothing for an empty one
+template <class T, class U>
+hipError_t upload(T** dst, const std::vector<U>& h)
+{
+    if (h.empty()) return hipSuccess;
+    const hipError_t e = hipMalloc(dst, h.size() * sizeof(U));
+    return e != hipSuccess ? e : hipMemcpy(const_cast<U*>(*dst), h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice);
+}
 
 } // namespace
 
@@ -1076,11 +885,7 @@ struct nsh_fir_casc_plan {
     float2* F = nullptr;
     float2* tw = nullptr;
     float* heq = nullptr;
-    float* stap = nullptr; // stage taps, concatenated (non-finite frames)
-    int nst = 0;           // stages the non-finite path runs (0: composite direct form)
-    int sl[MAX_STAGES] = {};
-    int sd[MAX_STAGES] = {};
-    int n1 = 0;
+    pfft_chain ch = {}; // the stages the non-finite path runs (0: composite direct form); owns ch.stap
     std::string kernel;
 
     nsh_fir_casc_plan() = default;
@@ -1091,19 +896,9 @@ struct nsh_fir_casc_plan {
         nsh::dev_free(F);
         nsh::dev_free(tw);
         nsh::dev_free(heq);
-        nsh::dev_free(stap);
+        nsh::dev_free(const_cast<float*>(ch.stap));
     }
 };
-
-#if NSH_PFFT_TRACE
-unsigned long long* g_pfft_trace = nullptr;
-extern "C" int nsh_pfft_trace_copy(unsigned long long* host) // probe builds only
-{
-    NSH_CK(hipDeviceSynchronize());
-    NSH_CK(hipMemcpy(host, g_pfft_trace, 64 * 16 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return 0;
-}
-#endif
 
 extern "C" {
 
@@ -1173,40 +968,29 @@ int nsh_fir_cascade_plan_create(int dev, const float* const* taps_host, const in
     if (nstages >= 2 && nstages <= MAX_STAGES) {
         const int n1 = (D * M - 1) / decims[0] + 1, n2 = (n1 - 1) / decims[1] + 1;
         if ((int64_t)(n1 + n2) <= (int64_t)D * IMG2) { // the smaller of both forms' image sets
-            p->nst = nstages;
-            p->n1 = n1;
+            p->ch.nst = nstages;
+            p->ch.n1 = n1;
             for (int s = 0; s < nstages; ++s) {
-                p->sl[s] = ntaps[s];
-                p->sd[s] = decims[s];
+                p->ch.sl[s] = ntaps[s];
+                p->ch.sd[s] = decims[s];
                 st.insert(st.end(), taps_host[s], taps_host[s] + ntaps[s]);
             }
         }
     }
-    if (e == hipSuccess && !st.empty()) e = hipMalloc(&p->stap, st.size() * sizeof(float));
-    if (e == hipSuccess && !st.empty()) e = hipMemcpy(p->stap, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&p->F, F.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc(&p->tw, tw.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc(&p->heq, hf.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->F, F.data(), F.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->heq, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload(&p->ch.stap, st);
+    if (e == hipSuccess) e = upload(&p->F, F);
+    if (e == hipSuccess) e = upload(&p->tw, tw);
+    if (e == hipSuccess) e = upload(&p->heq, hf);
     if (D == 16) {
         const char* fe = std::getenv("NSH_PFFT_FORM");
-        p->form = fe && *fe ? std::atoi(fe) : NSH_PFFT_FORM16;
+        p->form = fe && *fe ? std::atoi(fe) : FORM16;
         if (p->form != 1 && p->form != 2)
             return nsh::fail_msg("nsh_fir_cascade_plan_create: NSH_PFFT_FORM must be 1 or 2");
     }
-    if (e == hipSuccess) {
-        if (p->form == 2)
-            e = set_lds_attr((const void*)k_fir_pfft2<16>, lds_bytes2<16>(), p->dev);
-        else if (D == 16)
-            e = set_lds_attr((const void*)k_fir_pfft<16, PW16>, lds_bytes<16>(), p->dev);
-        else
-            e = set_lds_attr((const void*)k_fir_pfft<8, PW8>, lds_bytes<8>(), p->dev);
-    }
+    const pfft_form fm = form_of(D, p->form);
+    if (e == hipSuccess) e = set_lds_attr((const void*)fm.kernel, fm.lds, p->dev);
     if (e != hipSuccess) return nsh::fail(e, "nsh_fir_cascade_plan_create");
-    p->kernel = p->form == 2 ? std::string("k_fir_pfft2<16>")
-                             : "k_fir_pfft<" + std::to_string(D) + "," + std::to_string(D == 16 ? PW16 : PW8) + ">";
+    p->kernel = fm.name;
     *plan = p.release();
     return 0;
 }
@@ -1247,32 +1031,10 @@ int nsh_fir_cascade_ccf(void* plan, const float* in, const float* hist_in, float
     const int64_t max_wg = (int64_t)p->n_cu * p->wg_per_cu;
     int64_t wg = a.nf < max_wg ? a.nf : max_wg;
     a.fpw = (a.nf + wg - 1) / wg;
-    a.trace = nullptr;
-    a.stap = p->stap;
-    a.nst = p->nst;
-    a.n1 = p->n1;
-    for (int k = 0; k < MAX_STAGES; ++k) {
-        a.sl[k] = p->sl[k];
-        a.sd[k] = p->sd[k];
-    }
-#if NSH_PFFT_TRACE
-    {
-        static unsigned long long* tr = nullptr;
-        if (!tr) NSH_CK(hipMalloc(&tr, 64 * 16 * 8 * sizeof(unsigned long long)));
-        NSH_CK(hipMemsetAsync(tr, 0, 64 * 16 * 8 * sizeof(unsigned long long), nsh::S(stream)));
-        a.trace = tr;
-        g_pfft_trace = tr;
-    }
-#endif
+    a.ch = p->ch;
     wg = (a.nf + a.fpw - 1) / a.fpw;
-    if (p->form == 2)
-        nsh::launch((k_fir_pfft2<16>), dim3((unsigned)wg), dim3(64 * 16), lds_bytes2<16>(), nsh::S(stream), a);
-    else if (p->D == 16)
-        nsh::launch((k_fir_pfft<16, PW16>), dim3((unsigned)wg), dim3(pshape<16, PW16>::NT), lds_bytes<16>(),
-                    nsh::S(stream), a);
-    else
-        nsh::launch((k_fir_pfft<8, PW8>), dim3((unsigned)wg), dim3(pshape<8, PW8>::NT), lds_bytes<8>(),
-                    nsh::S(stream), a);
+    const pfft_form fm = form_of(p->D, p->form);
+    nsh::launch(fm.kernel, dim3((unsigned)wg), dim3(fm.nt), fm.lds, nsh::S(stream), a);
     NSH_CK_LAUNCH("nsh_fir_cascade_ccf");
     return 0;
 }

@@ -14,7 +14,7 @@ struct nsh_fir_plan {
     std::vector<float> taps_host;
     float* taps_dev = nullptr;
     // k_fir_mfma12 (decim 1): Q tap blocks of 32, S = 2Q k-steps of 16; the taps scaled by 2^sh8
-    // and split into two fp16 terms, reversed, as NSH_V12_COPIES shifted copies per plane
+    // and split into two fp16 terms, reversed, as V12_COPIES = 4 shifted copies per plane
     // (a lane's 8 taps of a k-step = two aligned 8-B reads)
     int Q = 0;
     int S = 0;

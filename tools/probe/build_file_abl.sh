@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds of libnsh_hip.so that differ only in one source file's compile flags:
 # build/abl/<stem>_<tag>.so for each "tag:FLAGS" argument. Usage:
-#   tools/probe/build_file_abl.sh nsh_fir_mfma "p0:" "p4k:-DNSH_V12_LDS_PAD=4096"
+#   tools/probe/build_file_abl.sh nsh_fir_pfft "base:" "o2:-O2"
 # Needs `make hip` first (reuses the other objects). Run on the CPU.
 set -e
 cd "$(dirname "$0")/../.."

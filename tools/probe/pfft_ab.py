@@ -1,6 +1,6 @@
 """A/B N builds of libnsh_hip.so on C5's fused chain (nsh_fir_cascade_ccf, 4 x fir(firwin(127,
 0.45), 2)) in one process: interleaved rounds, HIP events on one stream, >= 1 s warm-up; prints
-each build's median launch time and whether its output equals the first build's.
+each build's median, fastest and slowest round and whether its output equals the first build's.
 Usage: python tools/probe/pfft_ab.py A.so B.so [...]   (env: LOG2N=28 ROUNDS=8)"""
 import ctypes as C
 import json
@@ -59,5 +59,5 @@ for i, pth in enumerate(paths):
     same = bool(torch.equal(ys[i], ys[0]))
     rel = float((ys[i] - ys[0]).abs().max().item() / ys[0].abs().max().item())
     med = float(np.median(t[i]))
-    print(json.dumps({"lib": pth, "median_us": round(med, 1), "min_us": round(min(t[i]), 1),
+    print(json.dumps({"lib": pth, "median_us": round(med, 1), "min_us": round(min(t[i]), 1), "max_us": round(max(t[i]), 1),
                       "GSps_input": round(n / med / 1e3, 1), "same_as_first": same, "max_rel_diff": rel}), flush=True)
