@@ -2,9 +2,12 @@
 (rms error of the whole call and of its worst position, over the rms of the reference) held to a
 small factor of the same figures of an fp32 model that sums in the order the kernel's header documents.
 
-References: the float64 definitions on the same fp32 inputs (xlat_ref, resamp_ref, arb_ref, pfb_ref
-here, the synthesizer's polyphase model of tests/test_gpu_pfb_synth.py; fir_ref is xlat_ref untuned).
-tests/test_gpu_stream_forms.py takes its references and its fp32 emulation from here.
+References: the float64 definitions on the same fp32 inputs (xlat_ref, resamp_ref, arb_ref, pfb_ref,
+synth_ref; fir_ref is xlat_ref untuned), the one copy the GPU tests of each block import. resamp_ref and
+pfb_ref are polyphase sums; resamp_ref_conv and pfb_ref_conv are the same outputs by np.convolve
+straight from the definition, and test_cpu_references_agree holds each pair together.
+tests/test_gpu_stream_forms.py takes its fp32 emulation from here, and the plan geometry it shares
+with the CPU layout tests (the stream forms, below).
 
 Models: numpy, fp32 values carried in float64 arrays. One FMA is fl32(a b + c) with the product exact
 in double (_fma32's rule). Every model takes the switches of the CPU tests: fma=False rounds the
@@ -68,8 +71,10 @@ import math
 
 import numpy as np
 
+from oracle import oracle as orc
 from tests import fft_accuracy as fa
 from tests.fft_accuracy import MIN_FRAMES, MIN_OUTPUTS, frames_for, stats  # noqa: F401  (re-exported)
+from tests.gpu_util import dev, first_mismatch, host, int_signal, int_taps  # noqa: F401  (dev: re-exported)
 
 WHOLE, WORST = 1.25, 1.5
 
@@ -91,6 +96,14 @@ def ceil_div(a, b):
 
 
 # ---- the references, float64, per output ------------------------------------------------------------
+# hist = the samples before x[0], or None for zeros. Non-finite samples are data here (the tests that
+# plant a NaN or an Inf read where it lands), so the sums run with numpy's warnings off.
+def _ext(hist, H, x):
+    """[hist | x] in complex128, H zeros where hist is None."""
+    h0 = np.zeros(H, np.complex128) if hist is None else hist.astype(np.complex128)
+    return np.concatenate([h0, x.astype(np.complex128)])
+
+
 def phasors(first, n, inc):
     idx = (np.uint64(first % 2 ** 64) + np.arange(n, dtype=np.uint64))      # wraps mod 2^64
     p = idx * np.uint64(inc)
@@ -101,18 +114,19 @@ def phasors(first, n, inc):
 def xlat_ref(x, hist, taps, D, inc, first, n_out):
     """y[m] = sum_k h[k] rot(x)[mD - k]; hist = the L-1 raw samples before x[0]."""
     L = len(taps)
-    ext = np.concatenate([hist.astype(np.complex128), x.astype(np.complex128)])
-    with np.errstate(over="ignore"):
+    ext = _ext(hist, L - 1, x)
+    with np.errstate(invalid="ignore", over="ignore"):
         ext = ext * phasors(first - (L - 1), ext.size, inc)
-    return np.convolve(ext, np.asarray(taps, np.float64))[L - 1::D][:n_out]
+        full = np.convolve(ext, np.asarray(taps, np.float64))
+    return full[L - 1::D][:n_out]
 
 
 def xlat_ref_at(x, hist, taps, D, inc, first, n_out):
     """xlat_ref's definition evaluated at the n_out decimated outputs alone, tap by tap in float64 (the
     full-rate convolution of 2^16 D samples with 1024 taps takes a minute at D = 64).
-    test_cpu_decimated_reference_is_xlat_ref holds the two together."""
+    test_cpu_references_agree holds the two together."""
     L = len(taps)
-    ext = np.concatenate([hist[:L - 1].astype(np.complex128), x.astype(np.complex128)])
+    ext = _ext(None if hist is None else hist[:L - 1], L - 1, x)
     if inc:
         with np.errstate(over="ignore"):
             ext = ext * phasors(first - (L - 1), ext.size, inc)
@@ -134,26 +148,39 @@ def rotate_ref(x, inc, first):
 
 
 def resamp_ref(x, hist, taps, I, D, n_units):
-    """y[n] = sum_q h[phi + q I] x[j0 - q], phi = (n D) mod I, j0 = floor(n D / I); hist = the Q-1 samples before x[0]."""
+    """The polyphase sum: y[n] = sum_q h[phi + q I] x[j0 - q], phi = (n D) mod I, j0 = floor(n D / I);
+    hist = the Q-1 samples before x[0]."""
     L = len(taps)
     Q = ceil_div(L, I)
     H = Q - 1
-    ext = np.concatenate([hist.astype(np.complex128), x[:n_units * D].astype(np.complex128)])
+    ext = _ext(hist, H, x[:n_units * D])
     h = np.zeros(Q * I)
     h[:L] = taps
     n = np.arange(n_units * I)
     j0, phi = n * D // I, n * D % I
     y = np.zeros(n.size, np.complex128)
-    for q in range(Q):
-        y += h[phi + q * I] * ext[H + j0 - q]
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(Q):
+            y += h[phi + q * I] * ext[H + j0 - q]
     return y
 
 
+def resamp_ref_conv(x, hist, taps, I, D, n_units):
+    """The same from the definition: stuff I - 1 zeros between the samples, filter, keep every D-th."""
+    L = len(taps)
+    H = ceil_div(L, I) - 1
+    ext = _ext(hist, H, x[:n_units * D])
+    u = np.zeros(ext.size * I, np.complex128)
+    u[::I] = ext
+    return np.convolve(u, np.asarray(taps, np.float64))[H * I::D][:n_units * I]
+
+
 def arb_indices(step, F, phase, n_out):
-    """i, j (int64) and mu (float32, as the kernel forms it) of the outputs 0 .. n_out-1."""
-    pos = np.uint64(phase) + np.arange(n_out, dtype=np.uint64) * np.uint64(step)   # below 2^57 here
-    k = (pos >> np.uint64(32)).astype(np.int64)
-    frac = (pos & np.uint64(0xffffffff)).astype(np.uint32)
+    """i, j (int64) and mu (float32, as the kernel forms it) of the outputs 0 .. n_out-1. Positions in
+    Python integers: no phase or step wraps."""
+    pos = [phase + n * step for n in range(n_out)]
+    k = np.array([p >> 32 for p in pos], np.int64)
+    frac = np.array([p & 0xffffffff for p in pos], np.uint32)
     mu = (frac >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
     return k // F, k % F, mu
 
@@ -170,44 +197,72 @@ def arb_ref(x, hist, taps, F, step, phase, n_out):
     H = Q - 1
     i, j, mu = arb_indices(step, F, phase, n_out)
     assert i.max() < x.size
-    ext = np.concatenate([hist.astype(np.complex128), x.astype(np.complex128)])
+    ext = _ext(hist, H, x)
     h = np.asarray(taps, np.float64)
     d = diff_taps(taps).astype(np.float64)
     mu = mu.astype(np.float64)
     y = np.zeros(n_out, np.complex128)
-    for q in range(Q):
-        t = j + q * F
-        tc = np.minimum(t, L - 1)
-        y += np.where(t < L, (h[tc] + mu * d[tc]) * ext[i - q + H], 0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(Q):
+            t = j + q * F
+            tc = np.minimum(t, L - 1)
+            y += np.where(t < L, (h[tc] + mu * d[tc]) * ext[i - q + H], 0)
     return y
 
 
 def pfb_ref(x, hist, taps, M, n_out):
-    """(n_out, M): y[m][c] = sum_p u_p[m] exp(2j pi c p / M), u_p[m] = sum_q h[p + q M] x[(m - q) M - p];
-    hist = the L-1 samples before x[0]. Channels 0 and M/2 are the plain and the alternating sum of
-    the branches: exact on integer data."""
+    """The polyphase sum, (n_out, M): y[m][c] = sum_p u_p[m] exp(2j pi c p / M),
+    u_p[m] = sum_q h[p + q M] x[(m - q) M - p]; hist = the L-1 samples before x[0]. Channels 0 and M/2
+    are the plain and the alternating sum of the branches: exact on integer data."""
     L = len(taps)
     Q = ceil_div(L, M)
-    ext = np.concatenate([np.zeros(Q * M, np.complex128), hist.astype(np.complex128), x.astype(np.complex128)])
+    ext = np.concatenate([np.zeros(Q * M, np.complex128), _ext(hist, L - 1, x)])
     at0 = Q * M + L - 1                                   # x[0]
     h = np.zeros(Q * M)
     h[:L] = taps
     m, p = np.arange(n_out)[:, None], np.arange(M)[None, :]
     u = np.zeros((n_out, M), np.complex128)
-    for q in range(Q):
-        u += h[p + q * M] * ext[at0 + (m - q) * M - p]
     c = np.arange(M)
-    y = u @ np.exp(2j * np.pi * ((p.T * c[None, :]) % M) / M)
-    y[:, 0] = u.sum(axis=1)
-    y[:, M // 2] = (u * (1 - 2 * (p % 2))).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(Q):
+            u += h[p + q * M] * ext[at0 + (m - q) * M - p]
+        y = u @ np.exp(2j * np.pi * ((p.T * c[None, :]) % M) / M)
+        y[:, 0] = u.sum(axis=1)
+        y[:, M // 2] = (u * (1 - 2 * (p % 2))).sum(axis=1)
+    return y
+
+
+def pfb_ref_conv(x, hist, taps, M, n_out):
+    """The same from the definition, (n_out, M): channel c is the stream filtered by
+    h[k] exp(2j pi c k / M) and decimated by M."""
+    L = len(taps)
+    ext = _ext(hist, L - 1, x)
+    k = np.arange(L)
+    y = np.empty((n_out, M), np.complex128)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c in range(M):
+            hc = np.asarray(taps, np.float64) * np.exp(2j * np.pi * ((c * k) % M) / M)
+            y[:, c] = np.convolve(ext, hc)[L - 1::M][:n_out]
     return y
 
 
 def synth_ref(x, hist, taps, M):
-    """The synthesizer's float64 polyphase model (tests/test_gpu_pfb_synth.py), on flat arrays."""
-    from tests.test_gpu_pfb_synth import ref_of
-
-    return ref_of(x, hist if hist is not None and hist.size else None, taps, M)
+    """The synthesizer's polyphase model, n M outputs: v[m] = M ifft(X[m]) over the channels of every
+    item, y[m M + r] = sum_q h[r + q M] v_r[m - q]. x: n items of M, flat or (n, M); hist: the Q-1
+    items before them, flat or (Q-1, M), None or empty = zeros."""
+    L = len(taps)
+    Q = ceil_div(L, M)
+    hp = np.zeros(Q * M)
+    hp[:L] = taps
+    X = x.reshape(-1, M)
+    h0 = np.zeros((Q - 1, M), np.complex128) if hist is None or not hist.size else hist.reshape(Q - 1, M)
+    ext = np.concatenate([h0, X]).astype(np.complex128)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.fft.ifft(ext, axis=1) * M
+        y = np.zeros((X.shape[0], M), np.complex128)
+        for q in range(Q):
+            y += hp[q * M:(q + 1) * M][None, :] * v[Q - 1 - q:Q - 1 - q + X.shape[0]]
+    return y.reshape(-1)
 
 
 # ---- fp32 arithmetic in numpy -------------------------------------------------------------------------
@@ -310,11 +365,6 @@ def rotate_stream(raw, idx0, inc, bits=32, pair=True, fma=True):
 
 def rotate_model(x, inc, first, **kw):
     return _cplx(rotate_stream(x, first, inc, **kw))
-
-
-def xlat_form(D):
-    """(R, S) of k_fir_xlat by decimation (nsh_xlat.hip's instantiations)."""
-    return next((R, S) for top, R, S in [(4, 8, 1), (8, 4, 1), (16, 4, 2), (32, 4, 4), (64, 2, 4)] if D <= top)
 
 
 def xlat_model(x, hist, taps, D, inc, first, n_out, fma=True, **rot):
@@ -634,6 +684,270 @@ def split_bound(x, taps, D, n_out, halo):
     return b + (2.0 ** -24 * sum(terms) if L == 2 else 0.0)
 
 
+# ---- the FIR kernels' dispatch, restated (tests/test_gpu_fir_forms.py pins the lists) ----------------
+MAX_TAPS = 4096
+
+
+def q12(L):
+    return (L + 30) // 32 + 1
+
+
+def qf(L):
+    return (L + 30) // 16
+
+
+def fir_bucket_ends(bucket, supported):
+    """Smallest and largest L of every bucket among the tap counts the form accepts."""
+    ends = {}
+    for L in range(1, MAX_TAPS + 1):
+        if supported(L):
+            lo, hi = ends.get(bucket(L), (L, L))
+            ends[bucket(L)] = (min(lo, L), max(hi, L))
+    return sorted({L for lo_hi in ends.values() for L in lo_hi})
+
+
+ENDS_12 = fir_bucket_ends(q12, lambda L: q12(L) <= 6)
+ENDS_D = {D: fir_bucket_ends(lambda L, D=D: decim_qh(L, D), lambda L, D=D: decim_qh(L, D) <= 6) for D in (2, 4)}
+ENDS_F32 = fir_bucket_ends(qf, lambda L: qf(L) <= 17)
+DIRECT_R = {1: 8, 2: 8, 4: 4, 8: 2}
+# the first tap count past each matrix form's range: AUTO switches to the direct form there
+AUTO_DIRECT = {1: ENDS_12[-1] + 1, 2: ENDS_D[2][-1] + 1, 4: ENDS_D[4][-1] + 1}
+
+
+def direct_name(D):
+    return "k_fir_direct<%d,%d>" % (D, DIRECT_R[D])
+
+
+# ---- the stream kernels' dispatch, restated (tests/test_gpu_stream_forms.py pins the lists) ----------
+# k_fir_xlat<R,S>
+XLAT_BUCKETS = [(4, 8, 1), (8, 4, 1), (16, 4, 2), (32, 4, 4), (64, 2, 4)]   # (largest D, R, S)
+
+
+def xlat_form(D):
+    R, S = next((R, S) for top, R, S in XLAT_BUCKETS if D <= top)
+    a = 0
+    while (R * D) % (2 << a) == 0:     # 2^a: the largest power of two in R D
+        a += 1
+    return R, S, 256 * R // S, a
+
+
+def xlat_lc(L, S):
+    return ceil_div(ceil_div(L, S), 8) * 8
+
+
+def xlat_lds(D, L):
+    R, S, T, a = xlat_form(D)
+    wn = T * D + L + 8
+    return (wn + (wn >> a) + 1) * 8
+
+
+def bucket_ends(form, values):
+    ends = {}
+    for v in values:
+        lo, hi = ends.get(form(v), (v, v))
+        ends[form(v)] = (min(lo, v), max(hi, v))
+    return sorted({v for lo_hi in ends.values() for v in lo_hi})
+
+
+XLAT_ENDS = bucket_ends(lambda D: xlat_form(D)[:2], range(1, 65))
+XLAT_ODD = [3, 7, 63]      # odd D: the smallest LDS shift a of their R (the densest padding), one per R
+XLAT_TOPS = [top for top, _, _ in XLAT_BUCKETS]
+XLAT_LARGEST = max(((D, 1024) for D in range(1, 65)), key=lambda c: xlat_lds(*c))
+
+
+def xlat_cases():
+    cases = []
+    for D in sorted(set(XLAT_ENDS + XLAT_ODD)):
+        S = xlat_form(D)[1]
+        # 9: part 1 holds one tap, later parts none (S > 1); 8 S + 1: one past a multiple of 8 S
+        Ls = {1, 9, 8 * S + 1, 127}
+        if D in XLAT_TOPS or (D, 1024) == XLAT_LARGEST:
+            Ls |= {1023, 1024}
+        cases += [(D, L) for L in sorted(Ls)]
+    return cases
+
+
+# k_resamp<R,P>
+def resamp_form(I, D):
+    R, P = (8, 1) if D <= I else (8, 0) if D <= 2 * I else (4, 0) if D <= 4 * I else (2, 0) if D <= 8 * I else (1, 0)
+    G = max(1, min(256 // I, 8192 // (R * D)))
+    return R, P, G, G * R
+
+
+def resamp_shift(I, D):
+    """The a of a padded image (sample s at entry s + (s >> a)): among 31 (none), 6 .. 1 the first with
+    the smallest worst number of entries on one bank pair, over the groups of 32 lanes and 64 window
+    offsets (nsh_resamp.hip's worst_multiplicity; distinct entries only, so for I = 1 alone)."""
+    assert I == 1
+    R, P, G, U = resamp_form(I, D)
+    if P:
+        return 31
+    w = np.arange(-(-G // 32) * 32)
+    best, shift = 1 << 30, 31
+    for a in (31, 6, 5, 4, 3, 2, 1):
+        s = np.arange(64)[:, None] + w[None, :] * (R * D)
+        bank = ((s + (s >> min(a, 30))) & 31).reshape(64, -1, 32)
+        live = (w < G).reshape(1, -1, 32)
+        m = int(((bank[..., None] == np.arange(32)) & live[..., None]).sum(axis=2).max())
+        if m < best:
+            best, shift = m, a
+    return shift
+
+
+def resamp_lds(I, D, L):
+    R, P, G, U = resamp_form(I, D)
+    Q = ceil_div(L, I)
+    a = resamp_shift(I, D)
+    wn = U * D + Q - 1
+    hs_at = (max(wn + (wn >> a) + 1, U * I) + 1) // 2 * 2
+    return hs_at * 8 + Q * I * 4
+
+
+RESAMP_I = [1, 3, 7, 64]
+RESAMP_ODD_TILE = [(1, 37), (3, 37)]
+RESAMP_LONG = [(1, 1), (1, 2), (1, 4), (1, 8), (1, 9)]        # one pair per instantiation, Q = 1024 at L = 1024
+RESAMP_MOST_INPUTS = max(((1, D) for D in range(33, 65)), key=lambda c: resamp_form(*c)[3] * c[1])
+
+
+def resamp_pairs():
+    pairs = []
+    for I in RESAMP_I:
+        for D in (1, I, I + 1, 2 * I, 2 * I + 1, 4 * I, 4 * I + 1, 8 * I, 8 * I + 1, 64):
+            if 1 <= D <= 64 and (I, D) not in pairs:
+                pairs.append((I, D))
+    return pairs + RESAMP_ODD_TILE + [(63, 64), (64, 63)]
+
+
+def resamp_cases(largest=None):
+    cases = [(I, D, L) for I, D in resamp_pairs() for L in sorted({max(1, I - 1), I + 1})]
+    long_pairs = RESAMP_LONG + [RESAMP_MOST_INPUTS] + ([largest] if largest else [])
+    return cases + [(I, D, L) for I, D in dict.fromkeys(long_pairs) for L in (1023, 1024)]
+
+
+# the I = 1 pair with the largest LDS image at 1024 taps (recomputed and pinned by the CPU test below)
+RESAMP_LARGEST = (1, 42)
+
+
+# k_arb<R,P>: the step is s 2^27, the rate passed 32 F / s, s in [F / 2, 2048 F]
+def arb_form(F, L, s):
+    Q = ceil_div(L, F)
+    step, unit = s << 27, F << 32
+    t_fit = ((8192 - Q) * unit - 1) // step + 1
+    R, P = (4, 1) if step <= unit else (4, 0) if t_fit >= 1024 else (2, 0) if t_fit >= 512 else (1, 0)
+    return R, P, min(R * 256, t_fit) & ~1, t_fit
+
+
+def arb_boundaries(F, L):
+    """The s on both sides of every change of instantiation, the smallest (r = 64) and the largest
+    (r = 1/64): step == unit at s = 32 F, and t_fit, which never rises with s, by bisection."""
+    s_lo, s_hi = F // 2, 2048 * F
+    found = {s_lo, s_hi, 32 * F, 32 * F + 1}
+    for t in (1024, 512):
+        lo, hi = 32 * F + 1, s_hi           # t_fit(lo) >= t > t_fit(hi)
+        assert arb_form(F, L, lo)[3] >= t > arb_form(F, L, hi)[3]
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if arb_form(F, L, mid)[3] >= t else (lo, mid)
+        found |= {lo, hi}
+    return sorted(found)
+
+
+ARB_F = [2, 4, 32, 64]
+
+
+def arb_cases():
+    return [(F, L, s) for F in ARB_F for L in sorted({1, F + 1, 2047, 2048}) for s in arb_boundaries(F, L)]
+
+
+# k_pfb<M>
+PFB_M = [2, 4, 8, 16, 32, 64]
+
+
+def pfb_qmax(M):
+    return min(32, 1024 // M)       # at most 32 taps per branch and 1024 taps
+
+
+def pfb_lds(M, L):
+    """The window rows (one free row after every 8 below M = 32), the taps padded to 4 rows, 4 store images."""
+    T, Q = 2048 // M, ceil_div(L, M)
+    rows = T + Q - 1
+    return (rows + (rows >> 3) if M < 32 else rows) * M * 8 + ceil_div(Q, 4) * 4 * M * 4 + 4 * (64 * 4 + 64) * 8
+
+
+def pfb_cases():
+    cases = []
+    for M in PFB_M:
+        Qm = pfb_qmax(M)
+        # Q = 1, 1, 2, 3 (Q mod 4 = 3), 5, and the longest filter with a partial and a full last row
+        Ls = {1, M - 1, M + 1, 3 * M - 1, 5 * M, (Qm - 1) * M + 1, Qm * M}
+        cases += [(M, L) for L in sorted(Ls)]
+    return cases
+
+
+# ---- the stream forms: data, checks, one guarded call ----------------------------------------------
+GUARD = 9 - 9j
+
+
+def float_taps(rng, L):
+    return (rng.choice([-1.0, 1.0], L) * rng.uniform(0.5, 1.0, L)).astype(np.float32)
+
+
+def make_data(data, L, n_in, H, seed):
+    """(taps, samples, the H samples before them) of one data class."""
+    rng = np.random.default_rng(seed)
+    if data == "int":
+        return int_taps(rng, L), int_signal(rng, n_in), int_signal(rng, max(H, 1))[:H]
+    return float_taps(rng, L), orc.synth(n_in, 5 + seed), orc.synth(max(H, 1), 10 ** 7 + seed)[:H]
+
+
+def check(data, what, y, ref):
+    """Integer data: bit for bit, the first mismatching index named. Float data: tol_ok."""
+    if data == "int":
+        y = np.asarray(y, np.complex128).ravel()
+        ref = np.asarray(ref, np.complex128).ravel()
+        print(what, first_mismatch(y, ref))
+        np.testing.assert_array_equal(y, ref, err_msg="%s: %s" % (what, first_mismatch(y, ref)))
+    else:
+        ok, err, scale = orc.tol_ok(y, ref)
+        print(what, "max error", err, "scale", scale)
+        assert ok, (what, err, scale)
+
+
+def check_hist(what, got, raw, end, H):
+    """hist_out: the H raw samples before stream sample `end`; raw = [history | samples]."""
+    want = raw[end:end + H]
+    np.testing.assert_array_equal(got, want, err_msg="%s hist_out: %s" % (what, first_mismatch(got, want)))
+
+
+def run_call(torch, n_items, H, off, call, aligned=None):
+    """One call into an output between guard words, 8 off bytes past a 16-byte boundary; returns
+    (the n_items outputs, hist_out). call(out pointer, hist_out tensor) launches."""
+    dho = torch.full((max(H, 1),), 5 + 5j, dtype=torch.complex64, device="cuda")
+    dy = torch.full((n_items + 8,), GUARD, dtype=torch.complex64, device="cuda")
+    o = 2 + off
+    p = dy.data_ptr() + 8 * o
+    assert dy.data_ptr() % 16 == 0 and p % 16 == 8 * off
+    if aligned is not None:
+        assert (p % 16 == 0) == aligned
+    call(p, dho)
+    y = host(dy)
+    assert np.all(y[:o] == GUARD) and np.all(y[o + n_items:] == GUARD), "guard words around the output overwritten"
+    return y[o:o + n_items].copy(), host(dho)[:H].copy()
+
+
+def _margin(y, ref):
+    err, scale = np.abs(y - ref), np.max(np.abs(ref))
+    return float(np.max(err / (1e-5 * np.abs(ref) + 1e-6 * scale)))
+
+
+def _large_small_large(run, large, small):
+    """Both plans exist before the first launch; the large image, the small one, the large one again."""
+    for plan in (large, small, large):
+        run(plan)
+    large[0].close()
+    small[0].close()
+
+
 # ---- positions ----------------------------------------------------------------------------------------
 def positions_matrix(D):
     """MFMA and exact forms: the outputs of one 2048-sample chunk."""
@@ -641,9 +955,7 @@ def positions_matrix(D):
 
 
 def positions_direct(D):
-    """k_fir_direct<D,R>: 256 lanes of R outputs (R: tests/test_gpu_fir_forms.py's DIRECT_R)."""
-    from tests.test_gpu_fir_forms import DIRECT_R
-
+    """k_fir_direct<D,R>: 256 lanes of R outputs."""
     return 256 * DIRECT_R[D]
 
 

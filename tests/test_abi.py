@@ -17,6 +17,41 @@ def declared(header):
     return sorted(set(re.findall(r"\b(nsh_\w+|nsr_\w+)\s*\(", txt)))
 
 
+_INT = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
+        "float": ctypes.c_float, "double": ctypes.c_double}
+CTYPES = {**_INT, "void": None, "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
+          "void**": ctypes.POINTER(ctypes.c_void_p), "char*": ctypes.c_char_p, "const char*": ctypes.c_char_p,
+          "float*": ctypes.POINTER(ctypes.c_float), "const float*": ctypes.POINTER(ctypes.c_float),
+          "const float* const*": ctypes.POINTER(ctypes.POINTER(ctypes.c_float)),
+          "int*": ctypes.POINTER(ctypes.c_int), "const int*": ctypes.POINTER(ctypes.c_int),
+          "int64_t*": ctypes.POINTER(ctypes.c_int64), "uint64_t*": ctypes.POINTER(ctypes.c_uint64),
+          "size_t*": ctypes.POINTER(ctypes.c_size_t)}
+
+
+def spelling(decl):
+    """('const float*', 'taps_host') of 'const float *taps_host': the type with one space between words
+    and the stars attached, and the parameter's name ('' where the header gives none)."""
+    words = re.sub(r"(\*+)", r"\1 ", re.sub(r"\s*\*\s*", "*", decl)).split()
+    name = words.pop() if len(words) > 1 and re.fullmatch(r"\w+", words[-1]) else ""
+    return " ".join(words), name
+
+
+def prototypes(header):
+    """{name: (restype, [argtypes], [parameter names])} in ctypes, of every `ret nsh_name(params);` the
+    header declares. A spelling that CTYPES does not list raises, naming the entry."""
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)                           # preprocessor lines
+    protos = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(nsh_\w+)\s*\(([^()]*)\)\s*;", txt):
+        parts = [spelling(p) for p in params.split(",") if p.strip() and p.strip() != "void"]
+        for s in [spelling(ret + " _")[0]] + [p[0] for p in parts]:
+            if s not in CTYPES:
+                raise KeyError(f"{name}: no ctypes mapping for '{s}'")
+        protos[name] = (CTYPES[spelling(ret + " _")[0]], [CTYPES[s] for s, _ in parts], [n for _, n in parts])
+    return protos
+
+
 def exported(so):
     out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
     return {l.split()[-1] for l in out.splitlines() if l.strip()}
@@ -30,6 +65,42 @@ def test_hip_shim_exports_header():
     assert not missing, missing
     # the Python binding covers exactly the header
     assert sorted(nsh.SIGNATURES) == declared("nsh_hip.h")
+
+
+def _binding_names():
+    from newsched_amd import nsh
+
+    return sorted(nsh.SIGNATURES)
+
+
+@pytest.mark.parametrize("name", _binding_names())
+def test_binding_matches_the_prototype(name):
+    """nsh.SIGNATURES against include/nsh_hip.h: the restype and every argtype of every entry point, in
+    the header's order. One latitude: a float* or const float* parameter may be bound as c_void_p (a
+    device address) or as POINTER(c_float) (a host array); the binding uses both on purpose. The
+    header's names do not tell the two apart: the host arrays are *_host, all but nsh_event_elapsed_ms's
+    `float* ms`, a host out-parameter, so the rule "POINTER(c_float) iff *_host" fails on that one."""
+    from newsched_amd import nsh
+
+    restype, argtypes, names = prototypes("nsh_hip.h")[name]
+    floats = ctypes.POINTER(ctypes.c_float)
+    got_res, got_args = nsh.SIGNATURES[name]
+    assert got_res is restype, (name, got_res, restype)
+    assert len(got_args) == len(argtypes), (name, len(got_args), len(argtypes))
+    for i, (g, w) in enumerate(zip(got_args, argtypes)):
+        assert g is w or (w is floats and g is ctypes.c_void_p), (name, i, names[i], g, w)
+
+
+PLAN_ATTRS = [("ArbPlan", ("close", "__call__", "span")), ("PfbPlan", ("close", "__call__")),
+              ("PfbSynthPlan", ("close", "__call__")), ("ResampPlan", ("close", "__call__"))]
+
+
+@pytest.mark.parametrize("cls,attrs", PLAN_ATTRS, ids=[c for c, _ in PLAN_ATTRS])
+def test_plan_class_has_its_methods(cls, attrs):
+    from newsched_amd import nsh
+
+    for attr in attrs:
+        assert hasattr(getattr(nsh, cls), attr), (cls, attr)
 
 
 def test_hip_shim_loads_and_reports():

@@ -36,23 +36,6 @@ def indices(step, F, phase, n):
            [((phase + m * step) >> 32) % F for m in range(n)], [(phase + m * step) & 0xffffffff for m in range(n)]
 
 
-def test_arb_binding_covers_the_entries():
-    vp, i, i64, u64, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
-    P = ctypes.POINTER
-    assert nsh.SIGNATURES["nsh_arb_step"] == (i, [ctypes.c_double, i, P(u64)])
-    assert nsh.SIGNATURES["nsh_arb_span"] == (i, [u64, i, u64, i64, i64, P(i64), P(i64), P(u64)])
-    assert nsh.SIGNATURES["nsh_arb_plan_create"] == (i, [i, P(f), i, i, ctypes.c_double, P(vp)])
-    assert nsh.SIGNATURES["nsh_arb_plan_destroy"] == (i, [vp])
-    assert nsh.SIGNATURES["nsh_arb_tile"] == (i, [vp])
-    assert nsh.SIGNATURES["nsh_arb_kernel"] == (ctypes.c_char_p, [vp])
-    assert nsh.SIGNATURES["nsh_arb_history"] == (i, [vp])
-    assert nsh.SIGNATURES["nsh_arb_plan_step"] == (i, [vp, P(u64)])
-    assert nsh.SIGNATURES["nsh_arb_resamp_ccf"] == (i, [vp, vp, i64, vp, vp, vp, i64, u64, vp])
-    for attr in ("close", "__call__", "span"):
-        assert hasattr(nsh.ArbPlan, attr)
-    assert nsh.lib().nsh_abi_version() == 1
-
-
 def test_arb_plan_create_refuses_bad_arguments():
     L = nsh.lib()
     taps = (ctypes.c_float * 4)(0.25, 0.25, 0.25, 0.25)

@@ -1,24 +1,17 @@
 """CPU: the C-ABI of fft_filter_ccc (nsh_fft_filter_plan_create .. nsh_fft_filter_ccc) where it needs
 no GPU: every refusal happens before any HIP call, in the header's order, and leaves its message in
 nsh_last_error; n <= 0 is a no-op whatever the pointers; the accessors answer 0 or "" for a NULL
-plan; the binding's signatures are the header's."""
+plan. (The binding's signatures against the header: tests/test_abi.py.)"""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from newsched_amd import nsh
+from tests.gpu_util import ONE, TWO, refused
 
-ONE, TWO, THREE, FOUR = C.c_void_p(16), C.c_void_p(32), C.c_void_p(48), C.c_void_p(64)
+THREE, FOUR = C.c_void_p(48), C.c_void_p(64)
 BAD_SIZE = b"nsh_fft_filter_plan_create: fft_size must be 0, 1024, 2048, 4096 or 8192"
-
-
-def refused(rc, text):
-    assert rc != 0
-    msg = nsh.lib().nsh_last_error()
-    assert text in msg, msg
 
 
 def create(taps, fft_size=0, ntaps=None, out=True, null_taps=False):
@@ -127,29 +120,6 @@ def test_null_plan_accessors():
     assert L.nsh_fft_filter_tile(None) == 0
     assert L.nsh_fft_filter_kernel(None) == b""
     assert L.nsh_fft_filter_plan_destroy(None) == 0
-
-
-def test_signatures_match_the_header():
-    i, vp, i64, f = C.c_int, C.c_void_p, C.c_int64, C.c_float
-    want = {
-        "nsh_fft_filter_plan_create": (i, [i, C.POINTER(f), i, i, C.POINTER(vp)]),
-        "nsh_fft_filter_plan_destroy": (i, [vp]),
-        "nsh_fft_filter_fft_size": (i, [vp]),
-        "nsh_fft_filter_valid": (i, [vp]),
-        "nsh_fft_filter_history": (i, [vp]),
-        "nsh_fft_filter_tile": (i, [vp]),
-        "nsh_fft_filter_kernel": (C.c_char_p, [vp]),
-        "nsh_fft_filter_grid_cap": (i, [vp, i]),
-        "nsh_fft_filter_ccc": (i, [vp, vp, vp, vp, vp, i64, vp]),
-    }
-    for name, sig in want.items():
-        assert nsh.SIGNATURES[name] == sig, name
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "nsh_hip.h")).read(), flags=re.S)
-    for name, (_, args) in want.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, txt)
-        assert m, name
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
 
 
 def test_plan_class_raises_what_the_plan_refuses():

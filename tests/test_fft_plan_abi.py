@@ -1,23 +1,14 @@
 """CPU: the FFT plan's C-ABI (nsh_fft_plan_create .. nsh_fft_c2c) where it needs no GPU: every
 refusal happens before any HIP call and leaves its message in nsh_last_error, nframes <= 0 is a
-no-op whatever the pointers, the accessors answer 0 for a NULL plan, and the binding's signatures
-are the header's."""
+no-op whatever the pointers, and the accessors answer 0 for a NULL plan. (The binding's signatures against the
+header: tests/test_abi.py.)"""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from newsched_amd import nsh
-
-ONE, TWO = C.c_void_p(16), C.c_void_p(32)
-
-
-def refused(rc, text):
-    assert rc != 0
-    msg = nsh.lib().nsh_last_error()
-    assert text in msg, msg
+from tests.gpu_util import ONE, TWO, refused
 
 
 def create(size, window=None, out=True, inverse=0, shift=0):
@@ -78,29 +69,6 @@ def test_null_plan_accessors():
     assert L.nsh_fft_tile(None) == 0
     assert L.nsh_fft_kernel(None) == b""
     assert L.nsh_fft_plan_destroy(None) == 0
-
-
-def test_signatures_match_the_header():
-    i, vp, i64, f = C.c_int, C.c_void_p, C.c_int64, C.c_float
-    want = {
-        "nsh_fft_plan_create": (i, [i, i, i, C.POINTER(f), i, C.POINTER(vp)]),
-        "nsh_fft_plan_destroy": (i, [vp]),
-        "nsh_fft_plan_size": (i, [vp]),
-        "nsh_fft_tile": (i, [vp]),
-        "nsh_fft_kernel": (C.c_char_p, [vp]),
-        "nsh_fft_plan_grid_cap": (i, [vp, i]),
-        "nsh_fft_c2c": (i, [vp, vp, vp, i64, vp]),
-    }
-    for name, sig in want.items():
-        assert nsh.SIGNATURES[name] == sig, name
-    # ... and the header declares each with that many parameters
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "nsh_hip.h")).read(), flags=re.S)
-    for name, (_, args) in want.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, txt)
-        assert m, name
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
-    assert nsh.lib().nsh_abi_version() == 1
 
 
 @pytest.mark.parametrize("size", [0, 8, 24, 1000, 16384])

@@ -1,28 +1,21 @@
 """CPU: the C-ABI of freq_xlating_fft_filter_ccc (nsh_fft_xlat_plan_create .. nsh_fft_xlat_ccc) where
 it needs no GPU: every refusal happens before any HIP call, in the header's order, and leaves its
 message in nsh_last_error; n_out <= 0 is a no-op whatever the pointers; the accessors answer 0 or ""
-for a NULL plan; the binding's signatures are the header's; a plan's N, O, V and phase increment
+for a NULL plan (the binding's signatures against the header: tests/test_abi.py); a plan's N, O, V and phase increment
 against the Python model (a plan made where there is no device keeps its tables on the host); and the
 float64 reference of tests/test_gpu_fft_xlat.py against a term-by-term double sum."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from newsched_amd import nsh
 from tests import fft_xlat_ref as ref
+from tests.gpu_util import ONE, TWO, refused
 
-ONE, TWO, THREE, FOUR = C.c_void_p(16), C.c_void_p(32), C.c_void_p(48), C.c_void_p(64)
+THREE, FOUR = C.c_void_p(48), C.c_void_p(64)
 BAD_SIZE = b"nsh_fft_xlat_plan_create: fft_size must be 0, 1024, 2048, 4096 or 8192"
 BAD_DECIM = b"nsh_fft_xlat_plan_create: decimation must be a power of two in [1, 64]"
-
-
-def refused(rc, text):
-    assert rc != 0
-    msg = nsh.lib().nsh_last_error()
-    assert text in msg, msg
 
 
 def create(taps, decim=1, freq=0.0, fft_size=0, ntaps=None, out=True, null_taps=False):
@@ -143,32 +136,6 @@ def test_null_plan_accessors():
     inc = C.c_uint64()
     refused(L.nsh_fft_xlat_phase_inc(None, C.byref(inc)), b"nsh_fft_xlat_phase_inc: null pointer")
     refused(L.nsh_fft_xlat_phase_inc(ONE, None), b"nsh_fft_xlat_phase_inc: null pointer")
-
-
-def test_signatures_match_the_header():
-    i, vp, i64, u64, f, d = C.c_int, C.c_void_p, C.c_int64, C.c_uint64, C.c_float, C.c_double
-    want = {
-        "nsh_fft_xlat_plan_create": (i, [i, C.POINTER(f), i, i, d, i, C.POINTER(vp)]),
-        "nsh_fft_xlat_plan_destroy": (i, [vp]),
-        "nsh_fft_xlat_fft_size": (i, [vp]),
-        "nsh_fft_xlat_decim": (i, [vp]),
-        "nsh_fft_xlat_overlap": (i, [vp]),
-        "nsh_fft_xlat_valid": (i, [vp]),
-        "nsh_fft_xlat_history": (i, [vp]),
-        "nsh_fft_xlat_phase_inc": (i, [vp, C.POINTER(u64)]),
-        "nsh_fft_xlat_tile": (i, [vp]),
-        "nsh_fft_xlat_kernel": (C.c_char_p, [vp]),
-        "nsh_fft_xlat_grid_cap": (i, [vp, i]),
-        "nsh_fft_xlat_ccc": (i, [vp, vp, vp, vp, vp, i64, u64, vp]),
-    }
-    for name, sig in want.items():
-        assert nsh.SIGNATURES[name] == sig, name
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "nsh_hip.h")).read(), flags=re.S)
-    for name, (_, args) in want.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, txt)
-        assert m, name
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
 
 
 def test_plan_class_raises_what_the_plan_refuses():

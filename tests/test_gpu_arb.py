@@ -13,35 +13,12 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import arb_indices, arb_ref, diff_taps
+from tests.gpu_util import assert_tol, dev, host
 
 pytestmark = pytest.mark.gpu
 
 M31 = 2 ** 31 - 1
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def diff_taps(taps):
-    t = np.asarray(taps, np.float32)
-    return np.concatenate([t[1:] - t[:-1], np.zeros(1, np.float32)]).astype(np.float32)
-
-
-def arb_indices(step, F, phase, n_out):
-    """i, j (int64) and mu (float32, as the kernel forms it) of the outputs 0 .. n_out-1."""
-    pos = [phase + n * step for n in range(n_out)]
-    k = np.array([p >> 32 for p in pos], np.int64)
-    frac = np.array([p & 0xffffffff for p in pos], np.uint32)
-    mu = (frac >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    return k // F, k % F, mu
 
 
 def windows(x, hist, taps, F, i, j):
@@ -52,16 +29,6 @@ def windows(x, hist, taps, F, i, j):
     for q in range(Q):
         t = j + q * F
         yield t < L, np.minimum(t, L - 1), ext, i - q + H
-
-
-def arb_ref(x, hist, taps, F, step, phase, n_out):   # hist: the Q-1 raw samples before x[0], or None
-    i, j, mu = arb_indices(step, F, phase, n_out)
-    h = np.asarray(taps, np.float64); d = diff_taps(taps).astype(np.float64)
-    y = np.zeros(n_out, np.complex128)
-    for valid, t, ext, xi in windows(x.astype(np.complex128), None if hist is None else hist.astype(np.complex128), taps, F, i, j):
-        xi = np.clip(xi, 0, ext.size - 1)
-        y += np.where(valid, (h[t] + mu.astype(np.float64) * d[t]) * ext[xi], 0)
-    return y
 
 
 def arb_emulate_fp32(x, hist, taps, F, step, phase, n_out):
@@ -75,12 +42,6 @@ def arb_emulate_fp32(x, hist, taps, F, step, phase, n_out):
         re = np.where(valid, (w * ext[xi].real + re).astype(np.float32), re)
         im = np.where(valid, (w * ext[xi].imag + im).astype(np.float32), im)
     return re + 1j * im
-
-
-def assert_tol(y, ref, what="", rel=1e-5):
-    ok, err, scale = orc.tol_ok(y, ref, rel=rel)
-    print(f"  {what}: max err {err:.3g} of scale {scale:.3g} ({err / scale if scale else 0:.2g})")
-    assert ok, (what, err, scale)
 
 
 @pytest.fixture(scope="module")

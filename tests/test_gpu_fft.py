@@ -16,22 +16,12 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.gpu_util import bits, dev, host
 
 pytestmark = pytest.mark.gpu
 
 OPS = ["fwd", "inv", "chan"]
 GUARD = complex(123.0, -77.0)
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def rand_w(seed):
@@ -92,10 +82,6 @@ def gpu(torch, op, x, w=W, in_off=0, out_off=0, w_off=0, tail=1024):
     assert np.all(y[:out_off] == g) and np.all(y[out_off + n:] == g), (op, n // 1024, in_off, out_off)
     assert y.size - n == out_off + tail
     return y[out_off:out_off + n]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def report(name, op, y, r, x, w=W):

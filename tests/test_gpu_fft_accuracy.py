@@ -44,6 +44,7 @@ import pytest
 
 from tests import fft_accuracy as acc
 from tests import fft_xlat_ref as ref
+from tests.gpu_util import dev, hann, uniform
 
 gpu = pytest.mark.gpu
 
@@ -51,15 +52,6 @@ FFT_SIZES = [16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]
 DIRS = pytest.mark.parametrize("inv", [False, True], ids=["fwd", "inv"])
 FREQ = 0.1137
 FIRST = 12345
-
-
-def uniform(n, seed):
-    r = np.random.default_rng(seed)
-    return (r.uniform(-1, 1, n) + 1j * r.uniform(-1, 1, n)).astype(np.complex64)
-
-
-def hann(N):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)).astype(np.float32)
 
 
 # ---- the models and references of the plain transforms --------------------------------------------
@@ -248,13 +240,8 @@ def test_cpu_gate_refuses_too_few_frames_or_outputs():
         acc.gate("2^15 outputs", r, r, r, 64)
 
 
-# ---- GPU: fft_vcc, fft1024, channelizer1024 --------------------------------------------------------
-def on_device(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def run_fft(torch, plan, x):
-    dx = on_device(torch, x)
+    dx = dev(torch, x)
     dy = torch.empty_like(dx)
     plan(dx, dy, x.size // plan.fft_size)
     torch.cuda.synchronize()
@@ -300,7 +287,7 @@ def test_fft1024(torch_cuda, inv):
     torch = torch_cuda
     F = 64
     x = uniform(F * 1024, 600)
-    dx = on_device(torch, x)
+    dx = dev(torch, x)
     dy = torch.empty_like(dx)
     nsh.fft1024(dx, dy, F, inverse=inv)
     torch.cuda.synchronize()
@@ -315,7 +302,7 @@ def test_channelizer1024(torch_cuda):
     torch = torch_cuda
     F = 64
     x, w = uniform(F * 1024, 601), uniform(1024, 602)
-    dx, dw = on_device(torch, x), on_device(torch, w)
+    dx, dw = dev(torch, x), dev(torch, w)
     dy = torch.empty_like(dx)
     nsh.channelizer1024(dx, dy, dw, F)
     torch.cuda.synchronize()
@@ -341,7 +328,7 @@ def test_fft_filter_ccc(torch_cuda, N, Lk):
     V = p.valid
     F = acc.frames_for(V)
     x, hist = uniform(F * V, 700 + N + L), uniform(L - 1, 701)
-    dx, dh = on_device(torch, x), on_device(torch, hist)
+    dx, dh = dev(torch, x), dev(torch, hist)
     dy, dho = torch.empty_like(dx), torch.empty_like(dh)
     p(dx, dh, dho, dy, x.size)
     torch.cuda.synchronize()
@@ -368,7 +355,7 @@ def test_freq_xlating_fft_filter_ccc(torch_cuda, N, D, freq):
     F = acc.frames_for(Vd, 512 if Vd < 1024 else 64)
     n_out = F * Vd
     x, hist = uniform(n_out * D, 800 + N + D), uniform(L - 1, 801)
-    dx, dh = on_device(torch, x), on_device(torch, hist)
+    dx, dh = dev(torch, x), dev(torch, hist)
     dy = torch.empty(n_out, dtype=torch.complex64, device="cuda")
     dho = torch.empty_like(dh)
     p(dx, dh, dho, dy, n_out, FIRST)

@@ -1,8 +1,8 @@
 """GPU: nsh_fft_filter_ccc (k_fft_xlat<N, 1, false>, overlap-save FIR with complex taps) at its four frame
 sizes through the fft_size override and under the default size rule on each side of its boundaries.
 
-Reference (float64, in this file): numpy.convolve of hist_in ++ in with the taps, both complex128.
-The header's bound, per output m of frame f = m // V of a call:
+Reference (float64, ref64 here): numpy.convolve of hist_in ++ in with the taps, both complex128.
+The header's bound (tests/fft_xlat_ref.py's at D = 1), per output m of frame f = m // V of a call:
     |y - y_ref| <= 1e-5 |y_ref| + 1e-6 * max|x over frame f's window| * sum_k |h[k]|
 Every tolerance test prints its worst err / bound beside the same ratio of an overlap-save with
 scipy.fft in complex64 on the same frames (a good fp32 transform); that ratio is reported here and
@@ -16,28 +16,15 @@ import numpy as np
 import pytest
 
 from newsched_amd import nsh
+from tests import fft_xlat_ref as ref
+from tests.fft_xlat_ref import SIZES, rule, worst
+from tests.gpu_util import bits, uniform
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1024, 2048, 4096, 8192]
 GUARD = complex(123.0, -77.0)
 NG = 2  # guard samples on each side of out and hist_out
 sizes = pytest.mark.parametrize("N", SIZES)
-
-
-def rule(L):
-    """The default size rule of the header: 1024 up to 256 taps, 2048 up to 512, 4096 up to 2048, 8192
-    above."""
-    return 1024 if L <= 256 else 2048 if L <= 512 else 4096 if L <= 2048 else 8192
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.complex64).view(np.uint32)
-
-
-def uniform(n, seed):
-    r = np.random.default_rng(seed)
-    return (r.uniform(-1, 1, n) + 1j * r.uniform(-1, 1, n)).astype(np.complex64)
 
 
 def taps_of(kind, L):
@@ -51,26 +38,9 @@ def taps_of(kind, L):
     return (ss.firwin(L, 0.15) * np.exp(2j * np.pi * 0.2 * np.arange(L))).astype(np.complex64)
 
 
-def stream_of(x, hist, H):
-    """hist_in ++ in as complex128 (zeros without a history)."""
-    h0 = np.zeros(H, np.complex128) if hist is None else np.asarray(hist, np.complex64).astype(np.complex128)
-    assert h0.size == H
-    return np.concatenate([h0, np.asarray(x, np.complex64).astype(np.complex128)])
-
-
 def ref64(x, h, hist=None):
     H = len(h) - 1
-    return np.convolve(stream_of(x, hist, H), np.asarray(h, np.complex64).astype(np.complex128))[H:H + len(x)]
-
-
-def bound(x, h, N, y_ref, hist=None):
-    """The header's bound for every output of one call."""
-    H, n = len(h) - 1, len(x)
-    V = N - H
-    nf = -(-n // V)
-    s = np.abs(np.concatenate([stream_of(x, hist, H), np.zeros(nf * V + N)]))
-    wmax = np.array([s[f * V:f * V + N].max() for f in range(nf)])  # window f starts at stream position fV
-    return 1e-5 * np.abs(y_ref) + 1e-6 * np.repeat(wmax, V)[:n] * np.abs(np.asarray(h, np.complex128)).sum()
+    return np.convolve(ref.stream_of(x, hist, H), np.asarray(h, np.complex64).astype(np.complex128))[H:H + len(x)]
 
 
 def standin(x, h, N, hist=None):
@@ -80,18 +50,12 @@ def standin(x, h, N, hist=None):
     H, n = len(h) - 1, len(x)
     V = N - H
     nf = -(-n // V)
-    s = np.concatenate([stream_of(x, hist, H), np.zeros(nf * V + N)]).astype(np.complex64)
+    s = np.concatenate([ref.stream_of(x, hist, H), np.zeros(nf * V + N)]).astype(np.complex64)
     Hs = np.fft.fft(np.asarray(h, np.complex128), N).astype(np.complex64)
     w = np.stack([s[f * V:f * V + N] for f in range(nf)])
     y = sf.ifft(sf.fft(w, axis=1) * Hs[None, :], axis=1)
     assert y.dtype == np.complex64
     return y[:, H:].ravel()[:n]
-
-
-def worst(y, y_ref, b):
-    e = np.abs(np.asarray(y).astype(np.complex128) - y_ref)
-    assert np.all(e[b == 0] == 0)
-    return float(np.max(e[b > 0] / b[b > 0])) if np.any(b > 0) else 0.0
 
 
 def run(torch, plan, x, hist=None, odd=0, want_hist=True):
@@ -115,14 +79,14 @@ def run(torch, plan, x, hist=None, odd=0, want_hist=True):
     assert np.all(ho[:odd + NG] == g) and np.all(ho[odd + NG + H:] == g), (plan.kernel, n, odd)
     tail = np.concatenate([np.zeros(H, np.complex64) if hist is None else np.asarray(hist, np.complex64),
                            np.asarray(x, np.complex64)])[n:]
-    assert np.array_equal(bits(ho[odd + NG:odd + NG + H]), bits(tail)), (plan.kernel, n, "hist_out")
+    assert np.array_equal(bits(ho[odd + NG:odd + NG + H], np.complex64), bits(tail, np.complex64)), (plan.kernel, n, "hist_out")
     return y[odd + NG:odd + NG + n]
 
 
 def check(name, plan, x, h, y, hist=None, printed=True):
     N = plan.fft_size
     r = ref64(x, h, hist)
-    b = bound(x, h, N, r, hist)
+    b = ref.bound(x, h, 1, N, r, hist)
     w = worst(y, r, b)
     if printed:
         print(f"{name} {plan.kernel} L={len(h)} n={len(x)}: worst err/bound {w:.4f}, "
@@ -181,7 +145,7 @@ def test_impulse_taps(torch_cuda, N, Lk, k0k):
     y = run(torch_cuda, p, x)
     # the delayed input times c, in double
     r = np.concatenate([np.zeros(k0), x.astype(np.complex128)])[:len(x)] * np.complex128(c)
-    b = bound(x, h, N, r)
+    b = ref.bound(x, h, 1, N, r)
     w = worst(y, r, b)
     print(f"impulse {p.kernel} L={L} k0={k0}: worst err/bound {w:.4f}")
     assert w <= 1.0
@@ -225,7 +189,7 @@ def test_eight_byte_alignment(torch_cuda, N, L):
     hist = uniform(L - 1, 22)
     y0 = run(torch_cuda, p, x, hist, odd=0)
     y1 = run(torch_cuda, p, x, hist, odd=1)
-    assert np.array_equal(bits(y0), bits(y1))
+    assert np.array_equal(bits(y0, np.complex64), bits(y1, np.complex64))
     check("aligned", p, x, h, y0, hist)
     p.close()
 
@@ -239,9 +203,9 @@ def test_grid_cap_does_not_change_the_bits(torch_cuda, N):
     y0 = run(torch_cuda, p, x)
     for cap in (1, 2):
         p.grid_cap(cap)
-        assert np.array_equal(bits(run(torch_cuda, p, x)), bits(y0)), cap
+        assert np.array_equal(bits(run(torch_cuda, p, x), np.complex64), bits(y0, np.complex64)), cap
     p.grid_cap(0)
-    assert np.array_equal(bits(run(torch_cuda, p, x)), bits(y0))
+    assert np.array_equal(bits(run(torch_cuda, p, x), np.complex64), bits(y0, np.complex64))
     check("grid cap", p, x, h, y0)
     p.close()
 
@@ -272,7 +236,7 @@ def test_appended_samples_leave_complete_frames_alone(torch_cuda, N, L):
     n1 = 3 * V + 123  # frames 0..2 end inside it: their windows end at 3V
     ya = run(torch_cuda, p, x[:n1])
     yb = run(torch_cuda, p, x)
-    assert np.array_equal(bits(ya[:3 * V]), bits(yb[:3 * V]))
+    assert np.array_equal(bits(ya[:3 * V], np.complex64), bits(yb[:3 * V], np.complex64))
     check("short", p, x[:n1], h, ya, printed=False)
     check("long", p, x, h, yb, printed=False)
     p.close()
@@ -301,7 +265,7 @@ def test_nonfinite_sample_stays_in_its_frames(torch_cuda, bad, N, L, where):
     for f in hit:
         mask[f * V:(f + 1) * V] = True
     assert not np.any(np.isfinite(y[mask].real) & np.isfinite(y[mask].imag))
-    assert np.array_equal(bits(y[~mask]), bits(clean[~mask]))
+    assert np.array_equal(bits(y[~mask], np.complex64), bits(clean[~mask], np.complex64))
     p.close()
 
 
@@ -325,7 +289,7 @@ def test_against_the_direct_form(torch_cuda):
     d(dx, hin, hout, dy, len(x))
     torch.cuda.synchronize()
     r = ref64(x, h)
-    b = bound(x, h, p.fft_size, r)
+    b = ref.bound(x, h, 1, p.fft_size, r)
     wf, wd = worst(y, r, b), worst(dy.cpu().numpy(), r, b)
     print(f"real 127 taps: {p.kernel} err/bound {wf:.4f}, {d.kernel} err/bound {wd:.4f}")
     assert wf <= 1.0 and wd <= 1.0

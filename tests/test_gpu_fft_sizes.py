@@ -19,6 +19,7 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.gpu_util import bits, dev, hann, host, rand_window
 
 pytestmark = pytest.mark.gpu
 
@@ -29,32 +30,9 @@ both = pytest.mark.parametrize("inv", [False, True], ids=DIRS)
 sizes = pytest.mark.parametrize("N", SIZES)
 
 
-def dev(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # a writable copy: shared inputs are read-only
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def swap(a, N):
     """The halves of every frame of N swapped."""
     return np.ascontiguousarray(np.fft.fftshift(np.asarray(a).reshape(-1, N), axes=1)).ravel()
-
-
-def hann(N):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)).astype(np.float32)
-
-
-def rand_window(N, seed=5):
-    return np.random.default_rng(seed + N).uniform(-1, 1, N).astype(np.float32)
 
 
 def ref(x, N, inv, w=None, shift=False):

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from newsched_amd import nsh
+from tests.gpu_util import bits, uniform
 from tests import fft_xlat_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -33,15 +34,6 @@ GUARD = complex(123.0, -77.0)
 NG = 2  # guard samples on each side of out and hist_out
 FREQ = 0.1137
 sizes = pytest.mark.parametrize("N", SIZES)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.complex64).view(np.uint32)
-
-
-def uniform(n, seed):
-    r = np.random.default_rng(seed)
-    return (r.uniform(-1, 1, n) + 1j * r.uniform(-1, 1, n)).astype(np.complex64)
 
 
 def tone(n, inc, first=0, lo=0):
@@ -85,7 +77,7 @@ def run(torch, plan, x, hist=None, first=0, odd=0, want_hist=True):
     assert np.all(ho[:odd + NG] == g) and np.all(ho[odd + NG + H:] == g), (plan.kernel, n_out, odd)
     tail = np.concatenate([np.zeros(H, np.complex64) if hist is None else np.asarray(hist, np.complex64),
                            np.asarray(x[:n], np.complex64)])[n:]
-    assert np.array_equal(bits(ho[odd + NG:odd + NG + H]), bits(tail)), (plan.kernel, n_out, "hist_out")
+    assert np.array_equal(bits(ho[odd + NG:odd + NG + H], np.complex64), bits(tail, np.complex64)), (plan.kernel, n_out, "hist_out")
     return y[odd + NG:odd + NG + n_out]
 
 
@@ -157,7 +149,7 @@ def test_decimation_one_untuned_is_fft_filter_bit_for_bit(torch_cuda, N):
     dy, dho = torch.empty_like(dx), torch.empty_like(dh)
     q(dx, dh, dho, dy, len(x))
     torch.cuda.synchronize()
-    assert np.array_equal(bits(y), bits(dy.cpu().numpy()))
+    assert np.array_equal(bits(y, np.complex64), bits(dy.cpu().numpy(), np.complex64))
     p.close()
     q.close()
 
@@ -308,7 +300,7 @@ def test_null_history_is_a_zero_history(torch_cuda, N, D):
     x = uniform(frames_len(p, p.tile, 3), 8)
     y0 = run(torch_cuda, p, x, None, 5)
     y1 = run(torch_cuda, p, x, np.zeros(129, np.complex64), 5)
-    assert np.array_equal(bits(y0), bits(y1))
+    assert np.array_equal(bits(y0, np.complex64), bits(y1, np.complex64))
     p.close()
 
 
@@ -322,9 +314,9 @@ def test_grid_cap_does_not_change_the_bits(torch_cuda, N, D):
     y0 = run(torch_cuda, p, x, first=3)
     for cap in (1, 3):
         p.grid_cap(cap)
-        assert np.array_equal(bits(run(torch_cuda, p, x, first=3)), bits(y0)), cap
+        assert np.array_equal(bits(run(torch_cuda, p, x, first=3), np.complex64), bits(y0, np.complex64)), cap
     p.grid_cap(0)
-    assert np.array_equal(bits(run(torch_cuda, p, x, first=3)), bits(y0))
+    assert np.array_equal(bits(run(torch_cuda, p, x, first=3), np.complex64), bits(y0, np.complex64))
     check("grid cap", p, x, h, y0, None, 3)
     p.close()
 
@@ -338,7 +330,7 @@ def test_appended_samples_leave_complete_frames_alone(torch_cuda, N, D, L):
     n1 = (3 * Vd + 13) * D  # frames 0..2 end inside it: their windows end at 3V
     ya = run(torch_cuda, p, x[:n1], first=9)
     yb = run(torch_cuda, p, x, first=9)
-    assert np.array_equal(bits(ya[:3 * Vd]), bits(yb[:3 * Vd]))
+    assert np.array_equal(bits(ya[:3 * Vd], np.complex64), bits(yb[:3 * Vd], np.complex64))
     check("short", p, x[:n1], h, ya, None, 9)
     check("long", p, x, h, yb, None, 9)
     p.close()
@@ -367,7 +359,7 @@ def test_nan_sample_stays_in_its_frames(torch_cuda, N, D, L, where):
     for f in hit:
         mask[f * Vd:(f + 1) * Vd] = True
     assert not np.any(np.isfinite(y[mask].real) & np.isfinite(y[mask].imag))
-    assert np.array_equal(bits(y[~mask]), bits(clean[~mask]))
+    assert np.array_equal(bits(y[~mask], np.complex64), bits(clean[~mask], np.complex64))
     p.close()
 
 
@@ -382,7 +374,7 @@ def test_eight_byte_alignment(torch_cuda, N, D, L):
     hist = uniform(L - 1, 22)
     y0 = run(torch_cuda, p, x, hist, 3, odd=0)
     y1 = run(torch_cuda, p, x, hist, 3, odd=1)
-    assert np.array_equal(bits(y0), bits(y1))
+    assert np.array_equal(bits(y0, np.complex64), bits(y1, np.complex64))
     check("aligned", p, x, h, y0, hist, 3)
     p.close()
 

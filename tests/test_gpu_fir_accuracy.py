@@ -55,16 +55,12 @@ import pytest
 
 from tests import fir_accuracy as acc
 from tests.fft_xlat_ref import phase_inc
+from tests.gpu_util import dev, uniform
 
 gpu = pytest.mark.gpu
 
 FREQ = 0.1137
 FIRST = 12345
-
-
-def uniform(n, seed):
-    r = np.random.default_rng(seed)
-    return (r.uniform(-1, 1, n) + 1j * r.uniform(-1, 1, n)).astype(np.complex64)
 
 
 def lowpass(L, cutoff, seed, gain=1.0):
@@ -250,6 +246,45 @@ def test_cpu_decimated_reference_is_xlat_ref():
                                rtol=1e-15)
 
 
+def _pfb_pair(M, L):
+    h, x, H = uniform(L, 3 * L + M).real.copy(), uniform(40 * M, M), L - 1
+    return H, x, lambda hist: (acc.pfb_ref_conv(x, hist, h, M, 40), acc.pfb_ref(x, hist, h, M, 40))
+
+
+def _resamp_pair(I, D, L):
+    h, x, H = uniform(L, 5 * L + I).real.copy(), uniform(50 * D, I + D), acc.ceil_div(L, I) - 1
+    return H, x, lambda hist: (acc.resamp_ref_conv(x, hist, h, I, D, 50), acc.resamp_ref(x, hist, h, I, D, 50))
+
+
+def _xlat_pair(D, L):
+    h, x, H = uniform(L, 7 * L + D).real.copy(), uniform(30 * D, D), L - 1
+    inc, first = 0x1234567890abcdef, 2 ** 40 + 7
+    return H, x, lambda hist: (acc.xlat_ref_at(x, hist, h, D, inc, first, 30), acc.xlat_ref(x, hist, h, D, inc, first, 30))
+
+
+REFERENCE_PAIRS = [(_pfb_pair, c) for c in ((2, 5), (8, 127), (64, 1024))] + \
+                  [(_resamp_pair, c) for c in ((3, 2, 31), (1, 1, 1), (64, 7, 1024), (5, 64, 127))] + \
+                  [(_xlat_pair, c) for c in ((1, 127), (5, 33), (64, 1024))]
+
+
+@pytest.mark.parametrize("pair,case", REFERENCE_PAIRS,
+                         ids=["%s-%s" % (p.__name__[1:-5], "-".join(map(str, c))) for p, c in REFERENCE_PAIRS])
+def test_cpu_references_agree(pair, case):
+    """The two float64 derivations of one block's reference (np.convolve from the definition against
+    the polyphase sum; xlat_ref_at against xlat_ref) on a random history of full length, on hist=None
+    and on an explicit zero history: max|a - b| <= 1e-12 max|b|. The 1e-12 is float64's 1.1e-16 times
+    the 1024 terms of the longest sum, with a tenfold margin (the pairs stay below 1e-15 here);
+    an indexing defect in either form gives O(1)."""
+    H, x, both = pair(*case)
+    for what, hist in (("random", uniform(max(H, 1), 99 + H)[:H]), ("none", None), ("zeros", np.zeros(H, np.complex64))):
+        a, b = both(hist)
+        worst = np.max(np.abs(a - b)) / np.max(np.abs(b))
+        print("%s %s hist=%s: %.3g" % (pair.__name__, case, what, worst))
+        assert a.shape == b.shape and worst <= 1e-12, (case, what, worst)
+    for got, want in zip(both(None), both(np.zeros(H, np.complex64))):      # hist=None is a zero history, in each form
+        np.testing.assert_array_equal(got, want)
+
+
 def test_cpu_arb_model_without_mu_is_the_resampler_model():
     """(32, 32/21, 384) from phase 0: step = 21 2^32, mu = 0, w = h exactly: k_resamp's sum at I = 32, D = 21."""
     F, L, n = 32, 384, 32 * 40
@@ -350,15 +385,10 @@ def test_cpu_split_alone_models_meet_the_bound_and_defects_do_not(D, taps):
         assert use > 1.0 if over else model_use <= use <= 1.0, (D, taps, what, use)
 
 
-# ---- GPU ------------------------------------------------------------------------------------------------
-def on_device(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def run_stream(torch, plan, x, hist, n_items, *args):
     """One call of a stream plan (x, hist_in, hist_out, y, n, ...): returns the n_items outputs."""
-    dx = on_device(torch, x)
-    dh = on_device(torch, hist) if hist.size else None
+    dx = dev(torch, x)
+    dh = dev(torch, hist) if hist.size else None
     dho = torch.zeros(max(hist.size, 1), dtype=torch.complex64, device="cuda")
     dy = torch.empty(n_items, dtype=torch.complex64, device="cuda")
     plan(dx, dh, dho, dy, *args)
@@ -367,7 +397,7 @@ def run_stream(torch, plan, x, hist, n_items, *args):
 
 
 def run_fir(torch, plan, x, hist, n_out):
-    dx, dh = on_device(torch, x), on_device(torch, hist if hist.size else np.zeros(1, np.complex64))
+    dx, dh = dev(torch, x), dev(torch, hist if hist.size else np.zeros(1, np.complex64))
     dho = torch.zeros_like(dh)
     dy = torch.empty(n_out, dtype=torch.complex64, device="cuda")
     plan(dx, dh, dho, dy, n_out)
@@ -394,9 +424,7 @@ def fir_case(torch, D, L, algo, kernel, positions, model, seed):
 def test_fir_direct(torch_cuda, D, L):
     """k_fir_direct<D,R> at every decimation, and at 3617 taps (a window past 64 KiB of LDS)."""
     from newsched_amd import nsh
-    from tests.test_gpu_fir_forms import direct_name
-
-    name, y, model, r, F, _ = fir_case(torch_cuda, D, L, nsh.FIR_DIRECT, direct_name(D), acc.positions_direct(D),
+    name, y, model, r, F, _ = fir_case(torch_cuda, D, L, nsh.FIR_DIRECT, acc.direct_name(D), acc.positions_direct(D),
                                        lambda x, hist, h, n: acc.fir_model(x, hist, h, D, n), 1000 + L + D)
     acc.gate(name, y, model, r, F)
 
@@ -405,9 +433,7 @@ def test_fir_direct(torch_cuda, D, L):
 @pytest.mark.parametrize("L", [127, 257])
 def test_fir_f32mfma(torch_cuda, L):
     from newsched_amd import nsh
-    from tests.test_gpu_fir_forms import qf
-
-    name, y, model, r, F, _ = fir_case(torch_cuda, 1, L, nsh.FIR_MFMA_F32, "k_fir_f32mfma<%d>" % qf(L), acc.positions_matrix(1),
+    name, y, model, r, F, _ = fir_case(torch_cuda, 1, L, nsh.FIR_MFMA_F32, "k_fir_f32mfma<%d>" % acc.qf(L), acc.positions_matrix(1),
                                        lambda x, hist, h, n: acc.f32mfma_model(x, hist, h, n), 2000 + L)
     acc.gate(name, y, model, r, F)
 
@@ -424,9 +450,7 @@ def split_gate(name, y, r, F, model, model4):
 
 
 def mfma12_lengths():
-    from tests.test_gpu_fir_forms import ENDS_12, q12
-
-    tops = {q12(L): L for L in ENDS_12}           # the last L of every bucket
+    tops = {acc.q12(L): L for L in acc.ENDS_12}           # the last L of every bucket
     return [tops[min(tops)], tops[max(tops)]]
 
 
@@ -436,10 +460,8 @@ def test_fir_mfma12(torch_cuda, which):
     """k_fir_mfma12<Q> at the top of its smallest (one tap) and its largest (161 taps) bucket. The hardware
     sits on neither grouping the gate was set up with but between them, on groups of 8: see the table."""
     from newsched_amd import nsh
-    from tests.test_gpu_fir_forms import q12
-
     L = mfma12_lengths()[which]
-    name, y, m4, r, F, (x, hist, h, n) = fir_case(torch_cuda, 1, L, nsh.FIR_MFMA, "k_fir_mfma12<%d>" % q12(L),
+    name, y, m4, r, F, (x, hist, h, n) = fir_case(torch_cuda, 1, L, nsh.FIR_MFMA, "k_fir_mfma12<%d>" % acc.q12(L),
                                                   acc.positions_matrix(1),
                                                   lambda x, hist, h, n: acc.mfma12_model(x, hist, h, n, 4), 3000 + L)
     split_gate(name, y, r, F, lambda group: acc.mfma12_model(x, hist, h, n, group), m4)
@@ -472,7 +494,7 @@ def test_fir_xlat(torch_cuda, D, L, freq):
     from newsched_amd import nsh
 
     plan = nsh.FirXlatPlan(lowpass(L, 0.4 / D, 5000 + D + L), D, freq)
-    assert plan.kernel == "k_fir_xlat<%d,%d>" % acc.xlat_form(D), plan.kernel
+    assert plan.kernel == "k_fir_xlat<%d,%d>" % acc.xlat_form(D)[:2], plan.kernel
     assert (plan.inc == 0) == (freq == 0.0)
     F = acc.frames_for(plan.tile)
     n = F * plan.tile
@@ -493,7 +515,7 @@ def test_rotate(torch_cuda, first):
     n = F * acc.POSITIONS_ROTATE
     inc = nsh.phase_inc(FREQ)
     x = uniform(n, 5500)
-    dx = on_device(torch, x)
+    dx = dev(torch, x)
     dy = torch.empty_like(dx)
     assert dx.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0      # the 16-byte path, pairs from sample 0
     nsh.rotate_cc(dx, dy, n, inc, first)
@@ -538,7 +560,7 @@ def test_arb(torch_cuda, F, rate, L, phase):
     n_in = int(acc.arb_indices(step, F, phase, n)[0].max()) + 1
     assert plan.span(phase, n_in, n)[0] == n
     x, hist = uniform(n_in + 2, 7001 + F), uniform(max(plan.history, 1), 7002 + F)[:plan.history]
-    dx, dh = on_device(torch, x), on_device(torch, hist) if hist.size else None
+    dx, dh = dev(torch, x), dev(torch, hist) if hist.size else None
     dho = torch.zeros(max(hist.size, 1), dtype=torch.complex64, device="cuda")
     dy = torch.empty(n, dtype=torch.complex64, device="cuda")
     plan(dx, n_in, dh, dho, dy, n, phase)

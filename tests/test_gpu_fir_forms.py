@@ -19,19 +19,11 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import AUTO_DIRECT, DIRECT_R, ENDS_12, ENDS_D, ENDS_F32, direct_name, q12, qf
+from tests.fir_accuracy import decim_qh as qh
+from tests.gpu_util import dev, first_mismatch, host, int_signal, int_taps
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def run_fir(torch, plan, x, n_out, hist=None, null_hist=False):
@@ -42,44 +34,6 @@ def run_fir(torch, plan, x, n_out, hist=None, null_hist=False):
     dy = torch.empty(max(n_out, 1), dtype=torch.complex64, device="cuda")
     plan(dx, 0 if null_hist else hin, hout, dy, n_out)
     return host(dy)[:n_out], host(hout)[: L - 1]
-
-
-# ---- the dispatch, restated ------------------------------------------------------------------
-MAX_TAPS = 4096
-
-
-def q12(L):
-    return (L + 30) // 32 + 1
-
-
-def qh(L, D):
-    return (-(-L // D) + 31) // 16
-
-
-def qf(L):
-    return (L + 30) // 16
-
-
-def bucket_ends(bucket, supported):
-    """Smallest and largest L of every bucket among the tap counts the form accepts."""
-    ends = {}
-    for L in range(1, MAX_TAPS + 1):
-        if supported(L):
-            lo, hi = ends.get(bucket(L), (L, L))
-            ends[bucket(L)] = (min(lo, L), max(hi, L))
-    return sorted({L for lo_hi in ends.values() for L in lo_hi})
-
-
-ENDS_12 = bucket_ends(q12, lambda L: q12(L) <= 6)
-ENDS_D = {D: bucket_ends(lambda L, D=D: qh(L, D), lambda L, D=D: qh(L, D) <= 6) for D in (2, 4)}
-ENDS_F32 = bucket_ends(qf, lambda L: qf(L) <= 17)
-DIRECT_R = {1: 8, 2: 8, 4: 4, 8: 2}
-# the first tap count past each matrix form's range: AUTO switches to the direct form there
-AUTO_DIRECT = {1: ENDS_12[-1] + 1, 2: ENDS_D[2][-1] + 1, 4: ENDS_D[4][-1] + 1}
-
-
-def direct_name(D):
-    return "k_fir_direct<%d,%d>" % (D, DIRECT_R[D])
 
 
 def form_cases():
@@ -103,19 +57,6 @@ def test_fir_forms_bucket_end_points():
     assert AUTO_DIRECT == {1: 162, 2: 161, 4: 321}
 
 
-# ---- data -------------------------------------------------------------------------------------
-def int_signal(rng, n):
-    return (rng.integers(-8, 9, n) + 1j * rng.integers(-8, 9, n)).astype(np.complex64)
-
-
-def int_taps(rng, L):
-    h = rng.integers(-8, 9, L).astype(np.float32)
-    for i, v in ((0, 3.0), (L - 1, -5.0)):  # both end taps count
-        if h[i] == 0:
-            h[i] = v
-    return h
-
-
 def make_data(data, L, n_in, seed):
     """(taps, samples, history) of one data class."""
     rng = np.random.default_rng(seed)
@@ -123,15 +64,6 @@ def make_data(data, L, n_in, seed):
         return int_taps(rng, L), int_signal(rng, n_in), int_signal(rng, max(L - 1, 1))[: L - 1]
     h = (rng.standard_normal(L) * 0.1).astype(np.float32)
     return h, orc.synth(n_in, 5 + seed), orc.synth(max(L - 1, 1), 10 ** 7 + seed)[: L - 1]
-
-
-def first_mismatch(y, ref):
-    bad = np.nonzero(y != ref)[0]
-    if bad.size == 0:
-        return "equal"
-    i = int(bad[0])
-    return "%d of %d differ, first at %d (got %r, want %r), last at %d, differences %r" % (
-        bad.size, y.size, i, y[i], ref[i], int(bad[-1]), (y[bad[:8]] - ref[bad[:8]]).tolist())
 
 
 def check(data, what, y, ref):

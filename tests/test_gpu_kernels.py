@@ -11,19 +11,9 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.gpu_util import dev, host
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def test_synth_bit_exact(torch_cuda):

@@ -12,51 +12,19 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import pfb_ref_conv as pfb_ref
+from tests.gpu_util import assert_tol, dev, host, windowed_sinc
 
 pytestmark = pytest.mark.gpu
 
 
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def pfb_ref(x, hist, taps, M, n_out):
-    """(n_out, M) complex128; hist = the L-1 raw samples before x[0] (or None = zeros)."""
-    L = len(taps)
-    h0 = np.zeros(L - 1, np.complex128) if hist is None else hist.astype(np.complex128)
-    ext = np.concatenate([h0, x.astype(np.complex128)])
-    k = np.arange(L)
-    y = np.empty((n_out, M), np.complex128)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for c in range(M):
-            hc = np.asarray(taps, np.float64) * np.exp(2j * np.pi * ((c * k) % M) / M)
-            y[:, c] = np.convolve(ext, hc)[L - 1::M][:n_out]
-    return y
-
-
-def assert_tol(y, ref, what="", rel=1e-5):
-    ok, err, scale = orc.tol_ok(y, ref, rel=rel)
-    print(f"  {what}: max err {err:.3g} of scale {scale:.3g} ({err / scale if scale else 0:.2g})")
-    assert ok, (what, err, scale)
+def taps_for(L, M):
+    return windowed_sinc(L, M)
 
 
 @pytest.fixture(scope="module")
 def stream():
     return orc.synth(1 << 17, 2024)
-
-
-def taps_for(L, M):
-    t = np.hamming(L) if L > 2 else np.ones(L)
-    k = np.arange(L) - (L - 1) / 2.0
-    t = t * np.sinc(0.8 * k / M)
-    return (t / t.sum()).astype(np.float32)
 
 
 def run_pfb(torch, plan, x, hist, n_out, in_off=0, out_off=0):

@@ -1,6 +1,6 @@
 """GPU: nsh_pfb_synthesizer_ccf (k_pfb_synth<M>) through the C-ABI.
 
-Reference for every numeric check: synth_ref below, the polyphase model in numpy complex128 (an
+Reference for every numeric check: fir_accuracy.synth_ref (ref_of here), the polyphase model in numpy complex128 (an
 unnormalised inverse DFT across the channels of every item, then the M branch FIRs). Judged with
 oracle.tol_ok (1e-5) on the whole output jointly: the DFT mixes the channels, so the accuracy is
 relative to the loudest. Every case also checks that nothing outside the n_in * M outputs is written
@@ -12,59 +12,19 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import synth_ref as ref_of
+from tests.gpu_util import assert_tol, dev, host, windowed_sinc
 
 pytestmark = pytest.mark.gpu
 
 
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def synth_ref(X, hist, h, M):
-    """X (n, M); hist (Q-1, M) = the items before X[0]; returns n*M complex128."""
-    L = len(h)
-    Q = -(-L // M)
-    hp = np.zeros(Q * M)
-    hp[:L] = h
-    ext = np.concatenate([hist, X]).astype(np.complex128)
-    with np.errstate(invalid="ignore", over="ignore"):
-        v = np.fft.ifft(ext, axis=1) * M
-        y = np.zeros((X.shape[0], M), np.complex128)
-        for q in range(Q):
-            y += hp[q * M:(q + 1) * M][None, :] * v[Q - 1 - q:Q - 1 - q + X.shape[0]]
-    return y.reshape(-1)
-
-
-def ref_of(x, hist, taps, M):
-    """synth_ref on flat arrays; hist None = zeros."""
-    Q = -(-len(taps) // M)
-    h0 = np.zeros(((Q - 1), M), np.complex128) if hist is None else hist.reshape(Q - 1, M)
-    return synth_ref(x.reshape(-1, M), h0, np.asarray(taps, np.float64), M)
-
-
-def assert_tol(y, ref, what="", rel=1e-5):
-    ok, err, scale = orc.tol_ok(y, ref, rel=rel)
-    print(f"  {what}: max err {err:.3g} of scale {scale:.3g} ({err / scale if scale else 0:.2g})")
-    assert ok, (what, err, scale)
+def taps_for(L, M):
+    return windowed_sinc(L, M)
 
 
 @pytest.fixture(scope="module")
 def stream():
     return orc.synth(1 << 17, 2025)
-
-
-def taps_for(L, M):
-    t = np.hamming(L) if L > 2 else np.ones(L)
-    k = np.arange(L) - (L - 1) / 2.0
-    t = t * np.sinc(0.8 * k / M)
-    return (t / t.sum()).astype(np.float32)
 
 
 def run_synth(torch, plan, x, hist, n_in, in_off=0, out_off=0):

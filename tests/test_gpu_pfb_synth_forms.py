@@ -22,23 +22,9 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
-import tests.test_gpu_stream_forms as sf
+from tests import fir_accuracy as sf
 
 gpu = pytest.mark.gpu
-
-
-def synth_ref(X, hist, h, M):
-    """The normative model. X (n, M); hist (Q-1, M) = the items before X[0]; returns n*M complex128."""
-    L = len(h)
-    Q = -(-L // M)
-    hp = np.zeros(Q * M)
-    hp[:L] = h
-    ext = np.concatenate([hist, X]).astype(np.complex128)
-    v = np.fft.ifft(ext, axis=1) * M
-    y = np.zeros((X.shape[0], M), np.complex128)
-    for q in range(Q):
-        y += hp[q * M:(q + 1) * M][None, :] * v[Q - 1 - q:Q - 1 - q + X.shape[0]]
-    return y.reshape(-1)
 
 
 def branch_inputs(ext, M):
@@ -96,7 +82,7 @@ def test_synth_forms_reference_is_the_definition():
         Q, n = sf.ceil_div(L, M), 12
         x, hist = sf.int_signal(rng, n * M), sf.int_signal(rng, max((Q - 1) * M, 1))[:(Q - 1) * M]
         got = synth_ref_exact(x, hist, taps, M)
-        want = synth_ref(x.reshape(n, M), hist.reshape(Q - 1, M), taps.astype(np.float64), M).reshape(n, M)
+        want = sf.synth_ref(x, hist, taps, M).reshape(n, M)
         assert np.max(np.abs(got - want)) <= 1e-12 * np.max(np.abs(want))
         ext = np.concatenate([hist, x]).astype(np.complex128).reshape(-1, M)
         idx = np.arange((Q - 1 + n) * M)

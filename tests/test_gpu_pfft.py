@@ -23,35 +23,9 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.pfft_ref import C5, KERNEL16, _firwin, heq_l1, pfft_form, ref_chain, run_pfft  # noqa: F401  (pfft_form: autouse)
 
 pytestmark = pytest.mark.gpu
-
-KERNEL16 = {"2": "k_fir_pfft2<16>", "1": "k_fir_pfft<16,1>"}
-
-
-@pytest.fixture(autouse=True, params=["2", "1"], ids=["form2", "form1"])
-def pfft_form(request, monkeypatch):
-    monkeypatch.setenv("NSH_PFFT_FORM", request.param)
-    return request.param
-
-
-def _firwin(n, cutoff):
-    return np.asarray(__import__("scipy.signal", fromlist=["firwin"]).firwin(n, cutoff), np.float32)
-
-
-C5 = [(_firwin(127, 0.45), 2)] * 4
-
-
-def heq_l1(stages):
-    """sum |heq| of the composite filter (double)."""
-    h = np.ones(1)
-    dacc = 1
-    for t, d in stages:
-        u = np.zeros((t.size - 1) * dacc + 1)
-        u[::dacc] = t
-        h = np.convolve(h, u)
-        dacc *= d
-    return float(np.abs(h).sum())
 
 
 def tol_pfft(y, r, x, stages, rel=1e-5):
@@ -66,25 +40,6 @@ def tol_pfft(y, r, x, stages, rel=1e-5):
     maxerr = float(err.max()) if err.size else 0.0
     ok = maxerr <= rel * scale and bool(np.all(err <= rel * np.abs(r) + 0.1 * rel * scale))
     return ok, maxerr, scale
-
-
-def ref_chain(x, stages):
-    y = x
-    for h, d in stages:
-        y = orc.fir_ccf(y, h, d)
-    return y
-
-
-def run_pfft(torch, plan, x, n_out, hist=None, want_hist=True):
-    assert x.size == plan.decim * n_out
-    dx = torch.from_numpy(np.ascontiguousarray(x, np.complex64)).cuda() if x.size else \
-        torch.zeros(1, dtype=torch.complex64, device="cuda")
-    dh = torch.from_numpy(np.ascontiguousarray(hist, np.complex64)).cuda() if hist is not None else None
-    dho = torch.full((plan.hist_len,), complex(9.0, 9.0), dtype=torch.complex64, device="cuda") if want_hist else None
-    dy = torch.full((max(n_out, 1),), complex(7.0, 7.0), dtype=torch.complex64, device="cuda")
-    plan(dx, dh, dho, dy, n_out)
-    torch.cuda.synchronize()
-    return dy.cpu().numpy()[:n_out], (dho.cpu().numpy() if want_hist else None)
 
 
 def test_c5_plan_shape(torch_cuda, pfft_form):

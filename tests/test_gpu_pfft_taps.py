@@ -35,16 +35,10 @@ import scipy.signal as ss
 
 from oracle import oracle as orc
 from newsched_amd import nsh
-from tests.test_gpu_pfft import C5, KERNEL16, heq_l1, ref_chain, run_pfft
+from tests.pfft_ref import C5, KERNEL16, heq_l1, heq_of, pfft_form, ref_chain, run_pfft  # noqa: F401  (pfft_form: autouse)
 
 gpu = pytest.mark.gpu
 M, IMG2, MAX_STAGES = 512, 571, 8
-
-
-@pytest.fixture(autouse=True, params=["2", "1"], ids=["form2", "form1"])
-def pfft_form(request, monkeypatch):
-    monkeypatch.setenv("NSH_PFFT_FORM", request.param)
-    return request.param
 
 
 # ---------------------------------------------------------------- taps, composite, reference
@@ -53,18 +47,6 @@ def taps_u(n, seed, scale=1.0):
     """n taps, magnitudes uniform in [0.5, 1] * scale (a power of two), random signs."""
     rng = np.random.default_rng(seed)
     return (rng.uniform(0.5, 1.0, n) * rng.choice([-1.0, 1.0], n) * scale).astype(np.float32)
-
-
-def heq_of(stages):
-    """The composite filter in float64 from the fp32 stage taps (as heq_l1 composes it)."""
-    h = np.ones(1)
-    dacc = 1
-    for t, d in stages:
-        u = np.zeros((t.size - 1) * dacc + 1)
-        u[::dacc] = np.asarray(t, np.float64)
-        h = np.convolve(h, u)
-        dacc *= d
-    return h
 
 
 def geometry(stages):

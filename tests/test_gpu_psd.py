@@ -1,7 +1,7 @@
 """GPU: nsh_psd_cf (k_psd<N, LIN> and, past one segment, k_psd_sum): windowed FFT, |X|^2 and the sum
 over K frames in one pass.
 
-Reference (float64, in this file): the complex64 samples times the float32 window in double,
+Reference (float64, tests/psd_ref.py): the complex64 samples times the float32 window in double,
 numpy.fft.fft, |.|^2, the sum over the K frames of a vector, times scale. Bound per bin (tests 3, 4):
   B[k] = scale [sum_f (2 |X_f[k]| d_f + d_f^2) + g sum_f |X_f[k]|^2]
 with d_f = 1e-5 max_k |X_f[k]| (the project's per-frame FFT bound, oracle.tol_ok) and g = (K + 2) 2^-24
@@ -16,87 +16,13 @@ whatever N, and B / ref exceeds 0.1 only where K chi-square draws all fall very 
 Worst ratios printed by test 3 on one MI355X (err / B; the same for scipy's fp32 FFT followed by numpy
 fp32 squares and sums): see DESIGN.md section 4.9."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 from newsched_amd import nsh
-
-GUARD = np.float32(-12345.5)
-P_DEFAULT = 32  # the most frames of a segment; the GPU tests read it from a plan (segment())
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def hann(N):
-    return (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)).astype(np.float32)
-
-
-def rand_window(N, seed=5):
-    return np.random.default_rng(seed + N).uniform(-1, 1, N).astype(np.float32)
-
-
-def frames_per_team(N):
-    return max(1024 // N, 1)
-
-
-@functools.lru_cache(maxsize=None)
-def segment(N):
-    """P, the most frames of a segment at size N: K <= P runs one segment (one launch), K > P is cut
-    into ceil(K / P) segments of balanced_segment(K, P) frames. Read from a plan whose K is a multiple
-    of every candidate P."""
-    p = nsh.PsdPlan(N, 65536)
-    P = p.segment
-    p.close()
-    return P
-
-
-def balanced_segment(K, P):
-    nseg = -(-K // P)
-    return -(-K // nseg)
-
-
-@functools.lru_cache(maxsize=None)
-def signal(N, nframes, seed=1):
-    """Unit complex Gaussian noise plus the two tones (module docstring); read-only, shared."""
-    rng = np.random.default_rng(1000 * seed + N)
-    n = np.arange(N * nframes, dtype=np.float64)
-    a = 100.0 * np.sqrt(0.375 * N) / (N / 2)
-    x = (rng.standard_normal(n.size) + 1j * rng.standard_normal(n.size)) / np.sqrt(2.0)
-    x += a * np.exp(2j * np.pi * (N // 8) * n / N) + a * np.exp(2j * np.pi * (N // 3 + 0.37) * n / N)
-    x = x.astype(np.complex64)
-    x.setflags(write=False)
-    return x
-
-
-def reference(x, N, K, w=None, scale=1.0, shift=False):
-    """(ref, B) of whole vectors of x in float64, each (nvec, N)."""
-    f = np.asarray(x, np.complex64).astype(np.complex128).reshape(-1, N)
-    if w is not None:
-        f = f * np.asarray(w, np.float32).astype(np.float64)[None, :]
-    X = np.abs(np.fft.fft(f, axis=1))
-    d = 1e-5 * X.max(axis=1, keepdims=True)
-    lin = (2 * X * d + d * d).reshape(-1, K, N).sum(axis=1)
-    p = (X * X).reshape(-1, K, N).sum(axis=1)
-    g = (K + 2) * 2.0 ** -24
-    ref, B = scale * p, scale * (lin + g * p)
-    if shift:
-        ref, B = np.fft.fftshift(ref, axes=1), np.fft.fftshift(B, axes=1)
-    return ref, B
+from tests.gpu_util import bits, dev, hann, rand_window
+from tests.psd_ref import P_DEFAULT, balanced_segment, fft_of, frames_per_team, reference, run, segment, signal
 
 
 def yardstick(x, N, K, w, scale, shift):
@@ -110,33 +36,6 @@ def yardstick(x, N, K, w, scale, shift):
     assert y.dtype == np.complex64
     p = (y.real * y.real + y.imag * y.imag).reshape(-1, K, N).sum(axis=1, dtype=np.float32) * np.float32(scale)
     return np.fft.fftshift(p, axes=1) if shift else p
-
-
-def run(torch, plan, x, nvec=None, in_off=0, out_off=0, tail=64):
-    """plan over x; the input ends exactly at the end of its allocation (in_off samples of slack in
-    front), the output has out_off guard floats in front and `tail` behind, all checked."""
-    N, K = plan.fft_size, plan.navg
-    x = np.asarray(x, np.complex64)
-    if nvec is None:
-        nvec = x.size // (N * K)
-    assert x.size == nvec * N * K
-    dx = torch.zeros(in_off + x.size, dtype=torch.complex64, device="cuda")
-    dx[in_off:] = dev(torch, x)
-    dy = torch.full((out_off + nvec * N + tail,), float(GUARD), dtype=torch.float32, device="cuda")
-    plan(dx.data_ptr() + 8 * in_off, dy.data_ptr() + 4 * out_off, nvec)
-    y = host(dy)
-    assert np.all(y[:out_off] == GUARD) and np.all(y[out_off + nvec * N:] == GUARD), (plan.kernel, nvec, in_off, out_off)
-    return y[out_off:out_off + nvec * N].reshape(nvec, N)
-
-
-def fft_of(torch, x, N, w=None, shift=False):
-    p = nsh.FftPlan(N, False, w, shift)
-    dx = dev(torch, x)
-    dy = torch.empty_like(dx)
-    nsh.fft_c2c(p, dx, dy, x.size // N)
-    y = host(dy)
-    p.close()
-    return y
 
 
 gpu = pytest.mark.gpu
@@ -199,7 +98,7 @@ def test_impulse_frames_accumulate_exactly(torch_cuda, N):
         for nvec in (1, 2, 5):
             out = run(torch, plan, x[:nvec * K * N])
             want = (scale * p[:nvec * K].reshape(nvec, K).sum(axis=1)).astype(np.float32)
-            assert np.array_equal(bits(out), bits(np.repeat(want[:, None], N, axis=1))), (plan.kernel, K, nvec)
+            assert np.array_equal(bits(out, np.float32), bits(np.repeat(want[:, None], N, axis=1), np.float32)), (plan.kernel, K, nvec)
         plan.close()
 
 
@@ -225,7 +124,7 @@ def test_dc_frames_land_in_one_bin(torch_cuda, N):
             out = run(torch, plan, x[:3 * K * N])
             want = np.zeros((3, N), np.float32)
             want[:, N // 2 if shift else 0] = scale * p[:3 * K].reshape(3, K).sum(axis=1)
-            assert np.array_equal(bits(out), bits(want)), (plan.kernel, K, shift)
+            assert np.array_equal(bits(out, np.float32), bits(want, np.float32)), (plan.kernel, K, shift)
             plan.close()
 
 
@@ -302,7 +201,7 @@ def test_decibels(torch_cuda, N):
         z[1] = 0
         outz = run(torch, plan, z.ravel())
         assert np.all(np.isneginf(outz[1]))
-        assert np.array_equal(bits(outz[[0, 2]]), bits(out[[0, 2]]))
+        assert np.array_equal(bits(outz[[0, 2]], np.float32), bits(out[[0, 2]], np.float32))
         plan.close()
 
 
@@ -330,13 +229,13 @@ def test_cut_invariance(torch_cuda, N):
         whole = run(torch, plan, x)
         parts = np.concatenate([run(torch, plan, x[:2 * V]), run(torch, plan, x[2 * V:])])
         singles = np.concatenate([run(torch, plan, x[j * V:(j + 1) * V]) for j in range(5)])
-        assert np.array_equal(bits(whole), bits(parts)), (plan.kernel, K)
-        assert np.array_equal(bits(whole), bits(singles)), (plan.kernel, K)
+        assert np.array_equal(bits(whole, np.float32), bits(parts, np.float32)), (plan.kernel, K)
+        assert np.array_equal(bits(whole, np.float32), bits(singles, np.float32)), (plan.kernel, K)
         plan.grid_cap(2)
-        assert np.array_equal(bits(whole), bits(run(torch, plan, x))), (plan.kernel, K)
+        assert np.array_equal(bits(whole, np.float32), bits(run(torch, plan, x), np.float32)), (plan.kernel, K)
         plan.grid_cap(0)
-        assert np.array_equal(bits(whole), bits(run(torch, plan, x, in_off=1, out_off=1))), (plan.kernel, K)
-        assert np.array_equal(bits(whole), bits(run(torch, plan, x, in_off=3, out_off=7))), (plan.kernel, K)
+        assert np.array_equal(bits(whole, np.float32), bits(run(torch, plan, x, in_off=1, out_off=1), np.float32)), (plan.kernel, K)
+        assert np.array_equal(bits(whole, np.float32), bits(run(torch, plan, x, in_off=3, out_off=7), np.float32)), (plan.kernel, K)
         plan.close()
 
 
@@ -358,8 +257,8 @@ def test_more_rows_than_the_scratch_holds(torch_cuda, N, monkeypatch):
     monkeypatch.delenv("NSH_PSD_SCRATCH_BYTES")
     V = K * N
     singles = np.concatenate([run(torch, big, x[j * V:(j + 1) * V]) for j in range(7)])
-    assert np.array_equal(bits(run(torch, small, x)), bits(singles)), small.kernel
-    assert np.array_equal(bits(run(torch, big, x)), bits(singles)), big.kernel
+    assert np.array_equal(bits(run(torch, small, x), np.float32), bits(singles, np.float32)), small.kernel
+    assert np.array_equal(bits(run(torch, big, x), np.float32), bits(singles, np.float32)), big.kernel
     small.close()
     big.close()
 
@@ -393,7 +292,7 @@ def test_nonfinite_samples_stay_in_their_vector(torch_cuda, N):
             z[(K + K // 2) * N + N // 3] = complex(1.0, bad)
             out = run(torch, plan, z)
             assert not np.any(np.isfinite(out[1])), (plan.kernel, K, bad)
-            assert np.array_equal(bits(out[[0, 2]]), bits(clean[[0, 2]])), (plan.kernel, K, bad)
+            assert np.array_equal(bits(out[[0, 2]], np.float32), bits(clean[[0, 2]], np.float32)), (plan.kernel, K, bad)
         plan.close()
 
 

@@ -27,7 +27,8 @@ import numpy as np
 import pytest
 
 from newsched_amd import nsh
-from tests.test_gpu_psd import balanced_segment, bits, fft_of, frames_per_team, hann, reference, run, segment, signal
+from tests.gpu_util import bits, hann
+from tests.psd_ref import balanced_segment, fft_of, frames_per_team, reference, run, segment, signal
 
 gpu = pytest.mark.gpu
 KSEG = 32     # kSegment of nsh_psd.hip: the most frames of a segment by default
@@ -194,7 +195,7 @@ def test_chain_model_on_the_cpu(N):
         q = rng.integers(0, 201, (2, K, 24)).astype(np.float32)
         want = (0.25 * q.astype(np.float64).sum(axis=1)).astype(np.float32)
         assert K * 200 < 2 ** 24
-        assert np.array_equal(bits(chain_model(q, N, P, 0.25)), bits(want)), (N, K)
+        assert np.array_equal(bits(chain_model(q, N, P, 0.25), np.float32), bits(want, np.float32)), (N, K)
     assert {n for n, _ in seen} >= {1, 2, 3, 8, 9, 16, 17, 33, 129, 2048}
     if N == 16:
         assert all(g == 16 for n, g in seen if n > 1)  # 16 bins a group whatever nseg is
@@ -220,7 +221,8 @@ def test_exact_frames_on_the_cpu(pure):
                 if shift:
                     plain, model = np.fft.fftshift(plain, axes=1), np.fft.fftshift(model, axes=1)
                 want = ex.want(K, nvec, 0.25, shift)
-                assert np.array_equal(bits(want), bits(plain)) and np.array_equal(bits(want), bits(model)), (N, K, shift)
+                assert np.array_equal(bits(want, np.float32), bits(plain, np.float32)), (N, K, shift)
+                assert np.array_equal(bits(want, np.float32), bits(model, np.float32)), (N, K, shift)
 
 
 # ---- 2. the row walk ----------------------------------------------------------------------------
@@ -245,10 +247,10 @@ def test_row_walk_exact(torch_cuda, N):
             plan = nsh.PsdPlan(N, K, None, shift, scale)
             assert plan.segment == balanced_segment(K, P)
             assert nvec * -(-K // plan.segment) >= 2 * plan.tile + 3
-            want = bits(ex.want(K, nvec, scale, shift))
+            want = bits(ex.want(K, nvec, scale, shift), np.float32)
             for cap in (0, 1, 2):
                 plan.grid_cap(cap)
-                out = bits(run(torch, plan, x))
+                out = bits(run(torch, plan, x), np.float32)
                 bad = np.argwhere(out != want)
                 assert bad.size == 0, (plan.kernel, K, shift, cap, "first wrong (vector, bin):", bad[0], len(bad))
             plan.close()
@@ -276,7 +278,7 @@ def test_long_averages_exact(torch_cuda, N, K, monkeypatch):
         plan = nsh.PsdPlan(N, K, None, shift, scale)
         assert plan.segment == balanced_segment(K, KSEG)
         out = run(torch, plan, ex.take(K, nvec))
-        assert np.array_equal(bits(out), bits(ex.want(K, nvec, scale, shift))), (plan.kernel, K, shift)
+        assert np.array_equal(bits(out, np.float32), bits(ex.want(K, nvec, scale, shift), np.float32)), (plan.kernel, K, shift)
         plan.close()
     if batched:
         nseg = -(-K // balanced_segment(K, KSEG))
@@ -284,7 +286,8 @@ def test_long_averages_exact(torch_cuda, N, K, monkeypatch):
         small = nsh.PsdPlan(N, K, None, True, scale)
         monkeypatch.delenv("NSH_PSD_SCRATCH_BYTES")
         out = run(torch, small, ex.take(K, 3))
-        assert np.array_equal(bits(out), bits(ex.want(K, 3, scale, True))), (small.kernel, K, "batches of one vector")
+        assert np.array_equal(bits(out, np.float32), bits(ex.want(K, 3, scale, True), np.float32)), \
+            (small.kernel, K, "batches of one vector")
         small.close()
 
 
@@ -316,7 +319,7 @@ def test_chain_of_additions_is_the_documented_one(torch_cuda, N):
             if shift:
                 model = np.fft.fftshift(model, axes=1)
             out = run(torch, plan, x[:3 * K * N])
-            differ = int(np.sum(bits(out) != bits(model)))
+            differ = int(np.sum(bits(out, np.float32) != bits(model, np.float32)))
             assert differ == 0, (plan.kernel, K, shift, "bins that differ from the documented chain:", differ)
             plan.close()
 
@@ -364,8 +367,8 @@ def test_cut_invariance_across_groups(torch_cuda, N, K):
     whole = run(torch, plan, x)
     for j in (0, plan.tile - 1, plan.tile, nvec - 1):
         own = run(torch, plan, x[j * V:(j + 1) * V])
-        assert np.array_equal(bits(own[0]), bits(whole[j])), (plan.kernel, K, j)
-    assert np.array_equal(bits(whole), bits(run(torch, plan, x, in_off=1, out_off=3))), (plan.kernel, K)
+        assert np.array_equal(bits(own[0], np.float32), bits(whole[j], np.float32)), (plan.kernel, K, j)
+    assert np.array_equal(bits(whole, np.float32), bits(run(torch, plan, x, in_off=1, out_off=3), np.float32)), (plan.kernel, K)
     plan.close()
 
 
@@ -383,13 +386,13 @@ def test_segment_override(torch_cuda, N, K, nvec, monkeypatch):
     ex.check_transform(torch)
     x = ex.take(K, nvec)
     scale = 0.5
-    want = bits(ex.want(K, nvec, scale, False))
+    want = bits(ex.want(K, nvec, scale, False), np.float32)
     for s in (0, 1, 5, 64):
         monkeypatch.setenv("NSH_PSD_SEGMENT", str(s))
         plan = nsh.PsdPlan(N, K, None, False, scale)
         monkeypatch.delenv("NSH_PSD_SEGMENT")
         assert plan.segment == (K if s == 0 else balanced_segment(K, s)), (plan.kernel, s)
-        assert np.array_equal(bits(run(torch, plan, x)), want), (plan.kernel, s)
+        assert np.array_equal(bits(run(torch, plan, x), np.float32), want), (plan.kernel, s)
         plan.close()
 
 
@@ -426,5 +429,5 @@ def test_overflowing_power_stays_in_its_vector(torch_cuda, N):
             for name, z in (("one frame", one_big), ("the sum", two_half)):
                 out = run(torch, plan, z)
                 assert np.all(np.isposinf(out[1])), (plan.kernel, K, db, name)
-                assert np.array_equal(bits(out[[0, 2]]), bits(clean[[0, 2]])), (plan.kernel, K, db, name)
+                assert np.array_equal(bits(out[[0, 2]], np.float32), bits(clean[[0, 2]], np.float32)), (plan.kernel, K, db, name)
             plan.close()

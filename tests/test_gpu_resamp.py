@@ -11,46 +11,20 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import resamp_ref_conv as resamp_ref
+from tests.gpu_util import assert_tol, dev, host, windowed_sinc
 
 pytestmark = pytest.mark.gpu
 
 
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def resamp_ref(x, hist, taps, I, D, n_units):          # hist: the Q-1 raw samples before x[0], or None
-    L = len(taps); Q = -(-L // I); H = Q - 1
-    h0 = np.zeros(H, np.complex128) if hist is None else hist.astype(np.complex128)
-    ext = np.concatenate([h0, x[:n_units * D].astype(np.complex128)])
-    u = np.zeros(ext.size * I, np.complex128); u[::I] = ext
-    return np.convolve(u, np.asarray(taps, np.float64))[H * I::D][:n_units * I]
-
-
-def assert_tol(y, ref, what="", rel=1e-5):
-    ok, err, scale = orc.tol_ok(y, ref, rel=rel)
-    print(f"  {what}: max err {err:.3g} of scale {scale:.3g} ({err / scale if scale else 0:.2g})")
-    assert ok, (what, err, scale)
+def taps_for(L, I, D):
+    """Windowed sinc for resampling by I / D, gain I."""
+    return windowed_sinc(L, max(I, D), I)
 
 
 @pytest.fixture(scope="module")
 def stream():
     return orc.synth(1 << 17, 2024)
-
-
-def taps_for(L, I, D):
-    """Windowed sinc for resampling by I / D, gain I."""
-    t = np.hamming(L) if L > 2 else np.ones(L)
-    k = np.arange(L) - (L - 1) / 2.0
-    t = t * np.sinc(0.8 * k / max(I, D))
-    return (I * t / t.sum()).astype(np.float32)
 
 
 def run_resamp(torch, plan, x, hist, n_units, in_off=0, out_off=0, stream=None):

@@ -14,23 +14,13 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.gpu_util import dev, host
 
 pytestmark = pytest.mark.gpu
 
 GUARD = complex(9.0, -9.0)
 FLT_MAX = float(np.finfo(np.float32).max)
 TINY = float(np.float32(1e-45))  # the smallest subnormal, 2^-149
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def assert_bits(y, r, what=""):

@@ -44,193 +44,23 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
-# the float64 references per output and the fp32 emulation, shared with the accuracy gate
-from tests.fir_accuracy import (_emulate, _fma32, arb_indices, arb_ref, ceil_div, diff_taps, pfb_ref, phasors, resamp_ref,
-                                xlat_ref)
+# the float64 references per output and the fp32 emulation, shared with the accuracy gate; the dispatch
+# restated, the data classes and the checks, shared with tests/test_gpu_pfb_synth_forms.py and the CPU
+# layout tests
+from tests.fir_accuracy import (ARB_F, PFB_M, RESAMP_LARGEST, RESAMP_LONG, RESAMP_MOST_INPUTS, RESAMP_ODD_TILE, XLAT_ENDS,
+                                XLAT_LARGEST, XLAT_ODD, _emulate, _fma32, _large_small_large, _margin, arb_boundaries,
+                                arb_cases, arb_form, arb_indices, arb_ref, ceil_div, check, check_hist, diff_taps,
+                                float_taps, make_data, pfb_cases, pfb_lds, pfb_qmax, pfb_ref, phasors, resamp_cases,
+                                resamp_form, resamp_lds, resamp_pairs, resamp_ref, resamp_shift, run_call, xlat_cases,
+                                xlat_form, xlat_lc, xlat_lds, xlat_ref)
+from tests.gpu_util import dev, int_signal, int_taps
 
 gpu = pytest.mark.gpu
 
-GUARD = 9 - 9j
+
 FIRST = 2 ** 64 - 1000     # k_fir_xlat's first_index: the sample index wraps inside call 1
 PHASE_INT = (4 << 32) + (5 << 27)       # k_arb's start phases
 PHASE_FLOAT = (4 << 32) + 0x89abcdef
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-# ---- the dispatch, restated ------------------------------------------------------------------
-# k_fir_xlat<R,S>
-XLAT_BUCKETS = [(4, 8, 1), (8, 4, 1), (16, 4, 2), (32, 4, 4), (64, 2, 4)]   # (largest D, R, S)
-
-
-def xlat_form(D):
-    R, S = next((R, S) for top, R, S in XLAT_BUCKETS if D <= top)
-    a = 0
-    while (R * D) % (2 << a) == 0:     # 2^a: the largest power of two in R D
-        a += 1
-    return R, S, 256 * R // S, a
-
-
-def xlat_lc(L, S):
-    return ceil_div(ceil_div(L, S), 8) * 8
-
-
-def xlat_lds(D, L):
-    R, S, T, a = xlat_form(D)
-    wn = T * D + L + 8
-    return (wn + (wn >> a) + 1) * 8
-
-
-def bucket_ends(form, values):
-    ends = {}
-    for v in values:
-        lo, hi = ends.get(form(v), (v, v))
-        ends[form(v)] = (min(lo, v), max(hi, v))
-    return sorted({v for lo_hi in ends.values() for v in lo_hi})
-
-
-XLAT_ENDS = bucket_ends(lambda D: xlat_form(D)[:2], range(1, 65))
-XLAT_ODD = [3, 7, 63]      # odd D: the smallest LDS shift a of their R (the densest padding), one per R
-XLAT_TOPS = [top for top, _, _ in XLAT_BUCKETS]
-XLAT_LARGEST = max(((D, 1024) for D in range(1, 65)), key=lambda c: xlat_lds(*c))
-
-
-def xlat_cases():
-    cases = []
-    for D in sorted(set(XLAT_ENDS + XLAT_ODD)):
-        S = xlat_form(D)[1]
-        # 9: part 1 holds one tap, later parts none (S > 1); 8 S + 1: one past a multiple of 8 S
-        Ls = {1, 9, 8 * S + 1, 127}
-        if D in XLAT_TOPS or (D, 1024) == XLAT_LARGEST:
-            Ls |= {1023, 1024}
-        cases += [(D, L) for L in sorted(Ls)]
-    return cases
-
-
-# k_resamp<R,P>
-def resamp_form(I, D):
-    R, P = (8, 1) if D <= I else (8, 0) if D <= 2 * I else (4, 0) if D <= 4 * I else (2, 0) if D <= 8 * I else (1, 0)
-    G = max(1, min(256 // I, 8192 // (R * D)))
-    return R, P, G, G * R
-
-
-def resamp_shift(I, D):
-    """The a of a padded image (sample s at entry s + (s >> a)): among 31 (none), 6 .. 1 the first with
-    the smallest worst number of entries on one bank pair, over the groups of 32 lanes and 64 window
-    offsets (nsh_resamp.hip's worst_multiplicity; distinct entries only, so for I = 1 alone)."""
-    assert I == 1
-    R, P, G, U = resamp_form(I, D)
-    if P:
-        return 31
-    w = np.arange(-(-G // 32) * 32)
-    best, shift = 1 << 30, 31
-    for a in (31, 6, 5, 4, 3, 2, 1):
-        s = np.arange(64)[:, None] + w[None, :] * (R * D)
-        bank = ((s + (s >> min(a, 30))) & 31).reshape(64, -1, 32)
-        live = (w < G).reshape(1, -1, 32)
-        m = int(((bank[..., None] == np.arange(32)) & live[..., None]).sum(axis=2).max())
-        if m < best:
-            best, shift = m, a
-    return shift
-
-
-def resamp_lds(I, D, L):
-    R, P, G, U = resamp_form(I, D)
-    Q = ceil_div(L, I)
-    a = resamp_shift(I, D)
-    wn = U * D + Q - 1
-    hs_at = (max(wn + (wn >> a) + 1, U * I) + 1) // 2 * 2
-    return hs_at * 8 + Q * I * 4
-
-
-RESAMP_I = [1, 3, 7, 64]
-RESAMP_ODD_TILE = [(1, 37), (3, 37)]
-RESAMP_LONG = [(1, 1), (1, 2), (1, 4), (1, 8), (1, 9)]        # one pair per instantiation, Q = 1024 at L = 1024
-RESAMP_MOST_INPUTS = max(((1, D) for D in range(33, 65)), key=lambda c: resamp_form(*c)[3] * c[1])
-
-
-def resamp_pairs():
-    pairs = []
-    for I in RESAMP_I:
-        for D in (1, I, I + 1, 2 * I, 2 * I + 1, 4 * I, 4 * I + 1, 8 * I, 8 * I + 1, 64):
-            if 1 <= D <= 64 and (I, D) not in pairs:
-                pairs.append((I, D))
-    return pairs + RESAMP_ODD_TILE + [(63, 64), (64, 63)]
-
-
-def resamp_cases(largest=None):
-    cases = [(I, D, L) for I, D in resamp_pairs() for L in sorted({max(1, I - 1), I + 1})]
-    long_pairs = RESAMP_LONG + [RESAMP_MOST_INPUTS] + ([largest] if largest else [])
-    return cases + [(I, D, L) for I, D in dict.fromkeys(long_pairs) for L in (1023, 1024)]
-
-
-# the I = 1 pair with the largest LDS image at 1024 taps (recomputed and pinned by the CPU test below)
-RESAMP_LARGEST = (1, 42)
-
-
-# k_arb<R,P>: the step is s 2^27, the rate passed 32 F / s, s in [F / 2, 2048 F]
-def arb_form(F, L, s):
-    Q = ceil_div(L, F)
-    step, unit = s << 27, F << 32
-    t_fit = ((8192 - Q) * unit - 1) // step + 1
-    R, P = (4, 1) if step <= unit else (4, 0) if t_fit >= 1024 else (2, 0) if t_fit >= 512 else (1, 0)
-    return R, P, min(R * 256, t_fit) & ~1, t_fit
-
-
-def arb_boundaries(F, L):
-    """The s on both sides of every change of instantiation, the smallest (r = 64) and the largest
-    (r = 1/64): step == unit at s = 32 F, and t_fit, which never rises with s, by bisection."""
-    s_lo, s_hi = F // 2, 2048 * F
-    found = {s_lo, s_hi, 32 * F, 32 * F + 1}
-    for t in (1024, 512):
-        lo, hi = 32 * F + 1, s_hi           # t_fit(lo) >= t > t_fit(hi)
-        assert arb_form(F, L, lo)[3] >= t > arb_form(F, L, hi)[3]
-        while hi - lo > 1:
-            mid = (lo + hi) // 2
-            lo, hi = (mid, hi) if arb_form(F, L, mid)[3] >= t else (lo, mid)
-        found |= {lo, hi}
-    return sorted(found)
-
-
-ARB_F = [2, 4, 32, 64]
-
-
-def arb_cases():
-    return [(F, L, s) for F in ARB_F for L in sorted({1, F + 1, 2047, 2048}) for s in arb_boundaries(F, L)]
-
-
-# k_pfb<M>
-PFB_M = [2, 4, 8, 16, 32, 64]
-
-
-def pfb_qmax(M):
-    return min(32, 1024 // M)       # at most 32 taps per branch and 1024 taps
-
-
-def pfb_lds(M, L):
-    """The window rows (one free row after every 8 below M = 32), the taps padded to 4 rows, 4 store images."""
-    T, Q = 2048 // M, ceil_div(L, M)
-    rows = T + Q - 1
-    return (rows + (rows >> 3) if M < 32 else rows) * M * 8 + ceil_div(Q, 4) * 4 * M * 4 + 4 * (64 * 4 + 64) * 8
-
-
-def pfb_cases():
-    cases = []
-    for M in PFB_M:
-        Qm = pfb_qmax(M)
-        # Q = 1, 1, 2, 3 (Q mod 4 = 3), 5, and the longest filter with a partial and a full last row
-        Ls = {1, M - 1, M + 1, 3 * M - 1, 5 * M, (Qm - 1) * M + 1, Qm * M}
-        cases += [(M, L) for L in sorted(Ls)]
-    return cases
 
 
 # ---- CPU: the derived lists, pinned -------------------------------------------------------------
@@ -319,75 +149,6 @@ def test_stream_forms_pfb_case_list():
             nsh.PfbPlan(np.ones(pfb_qmax(M) * M + 1, np.float32), M)
 
 
-# ---- data -------------------------------------------------------------------------------------
-def int_signal(rng, n):
-    return (rng.integers(-8, 9, n) + 1j * rng.integers(-8, 9, n)).astype(np.complex64)
-
-
-def int_taps(rng, L):
-    h = rng.integers(-8, 9, L).astype(np.float32)
-    for i, v in ((0, 3.0), (L - 1, -5.0)):  # both end taps count
-        if h[i] == 0:
-            h[i] = v
-    return h
-
-
-def float_taps(rng, L):
-    return (rng.choice([-1.0, 1.0], L) * rng.uniform(0.5, 1.0, L)).astype(np.float32)
-
-
-def make_data(data, L, n_in, H, seed):
-    """(taps, samples, the H samples before them) of one data class."""
-    rng = np.random.default_rng(seed)
-    if data == "int":
-        return int_taps(rng, L), int_signal(rng, n_in), int_signal(rng, max(H, 1))[:H]
-    return float_taps(rng, L), orc.synth(n_in, 5 + seed), orc.synth(max(H, 1), 10 ** 7 + seed)[:H]
-
-
-def first_mismatch(y, ref):
-    bad = np.nonzero(y != ref)[0]
-    if bad.size == 0:
-        return "equal"
-    i = int(bad[0])
-    return "%d of %d differ, first at %d (got %r, want %r), last at %d, differences %r" % (
-        bad.size, y.size, i, y[i], ref[i], int(bad[-1]), (y[bad[:8]] - ref[bad[:8]]).tolist())
-
-
-def check(data, what, y, ref):
-    """Integer data: bit for bit, the first mismatching index named. Float data: tol_ok."""
-    if data == "int":
-        y = np.asarray(y, np.complex128).ravel()
-        ref = np.asarray(ref, np.complex128).ravel()
-        print(what, first_mismatch(y, ref))
-        np.testing.assert_array_equal(y, ref, err_msg="%s: %s" % (what, first_mismatch(y, ref)))
-    else:
-        ok, err, scale = orc.tol_ok(y, ref)
-        print(what, "max error", err, "scale", scale)
-        assert ok, (what, err, scale)
-
-
-def check_hist(what, got, raw, end, H):
-    """hist_out: the H raw samples before stream sample `end`; raw = [history | samples]."""
-    want = raw[end:end + H]
-    np.testing.assert_array_equal(got, want, err_msg="%s hist_out: %s" % (what, first_mismatch(got, want)))
-
-
-def run_call(torch, n_items, H, off, call, aligned=None):
-    """One call into an output between guard words, 8 off bytes past a 16-byte boundary; returns
-    (the n_items outputs, hist_out). call(out pointer, hist_out tensor) launches."""
-    dho = torch.full((max(H, 1),), 5 + 5j, dtype=torch.complex64, device="cuda")
-    dy = torch.full((n_items + 8,), GUARD, dtype=torch.complex64, device="cuda")
-    o = 2 + off
-    p = dy.data_ptr() + 8 * o
-    assert dy.data_ptr() % 16 == 0 and p % 16 == 8 * off
-    if aligned is not None:
-        assert (p % 16 == 0) == aligned
-    call(p, dho)
-    y = host(dy)
-    assert np.all(y[:o] == GUARD) and np.all(y[o + n_items:] == GUARD), "guard words around the output overwritten"
-    return y[o:o + n_items].copy(), host(dho)[:H].copy()
-
-
 def test_stream_forms_references_are_the_definitions():
     """The per-output references against the definitions the four older GPU files use (zero-stuff and
     convolve; one modulated convolution per channel), at small shapes."""
@@ -424,12 +185,6 @@ def test_stream_forms_references_are_the_definitions():
         i, j, mu = (pos >> 32) // F, (pos >> 32) % F, float(np.float32((pos & 0xffffffff) >> 8) * np.float32(2.0 ** -24))
         want = sum((float(taps[t]) + mu * float(d[t])) * raw[H + i - q] for q in range(H + 1) for t in [j + q * F] if t < L)
         assert got[n] == want, (n, got[n], want)
-
-
-# ---- CPU: the reference alone stays inside the tolerance ---------------------------------------------
-def _margin(y, ref):
-    err, scale = np.abs(y - ref), np.max(np.abs(ref))
-    return float(np.max(err / (1e-5 * np.abs(ref) + 1e-6 * scale)))
 
 
 def test_stream_forms_fp32_order_stays_inside_the_tolerance():
@@ -619,15 +374,6 @@ def test_stream_forms_pfb(torch_cuda, M, L, data):
     assert (plan.kernel, plan.tile) == ("k_pfb<%d>" % M, T), (plan.kernel, plan.tile)
     pfb_chain(torch_cuda, plan, data, h, x, hist, 2 * T + 77, 3, (M + L) & 1, "%s L=%d" % (plan.kernel, L))
     plan.close()
-
-
-# ---- GPU: two live plans of one instantiation with different LDS sizes -------------------------------------
-def _large_small_large(run, large, small):
-    """Both plans exist before the first launch; the large image, the small one, the large one again."""
-    for plan in (large, small, large):
-        run(plan)
-    large[0].close()
-    small[0].close()
 
 
 @gpu

@@ -11,6 +11,8 @@ import pytest
 
 from oracle import oracle as orc
 from newsched_amd import nsh
+from tests.fir_accuracy import phasors, xlat_ref
+from tests.gpu_util import assert_tol, dev, host, windowed_sinc
 
 pytestmark = pytest.mark.gpu
 
@@ -18,51 +20,13 @@ FREQS = [0.1, -0.37, 0.25, 1e-9, 0.4999999]
 BIG = 2**40 + 7
 
 
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def phasors(first, n, inc):
-    idx = (np.uint64(first % 2**64) + np.arange(n, dtype=np.uint64))      # wraps mod 2^64
-    p = idx * np.uint64(inc)
-    turns = (p >> np.uint64(11)).astype(np.float64) / 2.0**53
-    return np.exp(2j * np.pi * turns)
-
-
-def xlat_ref(x, hist, taps, D, inc, first, n_out):
-    """y[m] = sum_k h[k] rot(x)[mD - k]; hist = the L-1 raw samples before x[0] (or None = zeros)."""
-    L = len(taps)
-    h0 = np.zeros(L - 1, np.complex128) if hist is None else hist.astype(np.complex128)
-    ext = np.concatenate([h0, x.astype(np.complex128)])
-    with np.errstate(invalid="ignore", over="ignore"):
-        ext = ext * phasors(first - (L - 1), ext.size, inc)
-        full = np.convolve(ext, np.asarray(taps, np.float64))
-    return full[L - 1::D][:n_out]
-
-
-def assert_tol(y, ref, what=""):
-    ok, err, scale = orc.tol_ok(y, ref)
-    print(f"  {what}: max err {err:.3g} of scale {scale:.3g} ({err / scale if scale else 0:.2g})")
-    assert ok, (what, err, scale)
+def taps_for(L, D):
+    return windowed_sinc(L, D)
 
 
 @pytest.fixture(scope="module")
 def stream():
     return orc.synth(1 << 17, 2024)
-
-
-def taps_for(L, D):
-    t = np.hamming(L) if L > 2 else np.ones(L)
-    k = np.arange(L) - (L - 1) / 2.0
-    t = t * np.sinc(0.8 * k / D)
-    return (t / t.sum()).astype(np.float32)
 
 
 # ---- rotator ---------------------------------------------------------------------------------------

@@ -58,11 +58,3 @@ def test_pfb_null_plan_accessors():
     assert L.nsh_pfb_tile(None) == 0
     assert L.nsh_pfb_kernel(None) == b""
     assert L.nsh_pfb_plan_destroy(None) == 0
-
-
-def test_pfb_binding_covers_the_entries():
-    for name in ("nsh_pfb_plan_create", "nsh_pfb_plan_destroy", "nsh_pfb_tile", "nsh_pfb_kernel",
-                 "nsh_pfb_channelizer_ccf"):
-        assert name in nsh.SIGNATURES
-    for attr in ("close", "__call__"):
-        assert hasattr(nsh.PfbPlan, attr)

@@ -62,11 +62,3 @@ def test_synth_null_plan_accessors():
     assert L.nsh_pfb_synth_tile(None) == 0
     assert L.nsh_pfb_synth_kernel(None) == b""
     assert L.nsh_pfb_synth_plan_destroy(None) == 0
-
-
-def test_synth_binding_covers_the_entries():
-    for name in ("nsh_pfb_synth_plan_create", "nsh_pfb_synth_plan_destroy", "nsh_pfb_synth_tile",
-                 "nsh_pfb_synth_kernel", "nsh_pfb_synthesizer_ccf"):
-        assert name in nsh.SIGNATURES
-    for attr in ("close", "__call__"):
-        assert hasattr(nsh.PfbSynthPlan, attr)

@@ -1,28 +1,21 @@
 """CPU: the C-ABI of psd_vcf (nsh_psd_plan_create .. nsh_psd_cf) where it needs no GPU: every refusal
 happens before any HIP call, in the header's order, and leaves its message in nsh_last_error;
-nvec <= 0 is a no-op whatever the pointers; the accessors answer 0 or "" for a NULL plan; the binding's
-signatures are the header's. (The overflow refusal of nsh_psd_cf needs a plan's sizes and is checked on
+nvec <= 0 is a no-op whatever the pointers; the accessors answer 0 or "" for a NULL plan. (The binding's
+signatures against the header: tests/test_abi.py. The overflow refusal of nsh_psd_cf needs a plan's sizes and is checked on
 the GPU, tests/test_gpu_psd.py.)"""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from newsched_amd import nsh
+from tests.gpu_util import ONE, TWO, refused
 
-ONE, TWO = C.c_void_p(16), C.c_void_p(32)
+
 BAD_SIZE = b"nsh_psd_plan_create: fft_size must be a power of two in [16, 8192]"
 BAD_NAVG = b"nsh_psd_plan_create: navg must be in [1, 65536]"
 BAD_WINDOW = b"nsh_psd_plan_create: window entry is not finite"
 BAD_SCALE = b"nsh_psd_plan_create: scale must be finite and > 0"
-
-
-def refused(rc, text):
-    assert rc != 0
-    msg = nsh.lib().nsh_last_error()
-    assert text in msg, msg
 
 
 def create(fft_size, navg, window=None, scale=1.0, out=True, shift=0, db=0):
@@ -109,29 +102,6 @@ def test_null_plan_accessors():
     assert L.nsh_psd_tile(None) == 0
     assert L.nsh_psd_kernel(None) == b""
     assert L.nsh_psd_plan_destroy(None) == 0
-
-
-def test_signatures_match_the_header():
-    i, vp, i64, f = C.c_int, C.c_void_p, C.c_int64, C.c_float
-    want = {
-        "nsh_psd_plan_create": (i, [i, i, i, C.POINTER(f), i, f, i, C.POINTER(vp)]),
-        "nsh_psd_plan_destroy": (i, [vp]),
-        "nsh_psd_fft_size": (i, [vp]),
-        "nsh_psd_navg": (i, [vp]),
-        "nsh_psd_segment": (i, [vp]),
-        "nsh_psd_tile": (i, [vp]),
-        "nsh_psd_kernel": (C.c_char_p, [vp]),
-        "nsh_psd_grid_cap": (i, [vp, i]),
-        "nsh_psd_cf": (i, [vp, vp, vp, i64, vp]),
-    }
-    for name, sig in want.items():
-        assert nsh.SIGNATURES[name] == sig, name
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "nsh_hip.h")).read(), flags=re.S)
-    for name, (_, args) in want.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, txt)
-        assert m, name
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
 
 
 def test_plan_class_raises_what_the_plan_refuses():

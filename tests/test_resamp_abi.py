@@ -60,11 +60,3 @@ def test_resamp_null_plan_accessors():
     assert L.nsh_resamp_kernel(None) == b""
     assert L.nsh_resamp_history(None) == 0
     assert L.nsh_resamp_plan_destroy(None) == 0
-
-
-def test_resamp_binding_covers_the_entries():
-    for name in ("nsh_resamp_plan_create", "nsh_resamp_plan_destroy", "nsh_resamp_tile", "nsh_resamp_kernel",
-                 "nsh_resamp_history", "nsh_resamp_ccf"):
-        assert name in nsh.SIGNATURES
-    for attr in ("close", "__call__"):
-        assert hasattr(nsh.ResampPlan, attr)

@@ -6,7 +6,7 @@ chooser that went wrong after an edit would pass every parity test.
   * k_resamp: (R, G, a) for the 100 (I, D) pairs of tests/test_resamp_layout.py against its tile()
     and padding(), the model whose bank multiplicities that file asserts.
   * k_arb: (a, pad) for every (F, s) of the k_arb cases of tests/test_gpu_stream_forms.py (the steps
-    on both sides of every change of instantiation). That file restates the dispatch, not the
+    on both sides of every change of instantiation; tests/fir_accuracy.py holds the list). It restates the dispatch, not the
     layout, so a and pad are restated here, from nsh_arb.hip's header: 32 consecutive outputs at
     sampled phases, the shift a of the sample image among 31 (none), 6 .. 1 for r < 1, the pad of the
     taps' upper half row among 0 .. 31 for F = 64, the first candidate with the smallest worst
@@ -15,7 +15,7 @@ chooser that went wrong after an edit would pass every parity test.
 import numpy as np
 
 from tests.test_cpp_runtime import run
-from tests.test_gpu_stream_forms import arb_cases, arb_form
+from tests.fir_accuracy import arb_cases, arb_form
 from tests.test_resamp_layout import PAIRS, linear, padding, tile
 
 
