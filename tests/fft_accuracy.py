@@ -1,4 +1,4 @@
-"""What tests/test_gpu_fft_accuracy.py judges the FFT kernels by: the rms error of a whole call and of
+"""What tests/test_gpu_fft_accuracy.py and tests/test_gpu_pfft_accuracy.py judge the FFT kernels by: the rms error of a whole call and of
 its worst position, held to a small factor of the same figures of a numpy / scipy complex64 model of
 the same chain on the same frames.
 
@@ -57,3 +57,45 @@ def gate(name, y, model, r, frames, whole=WHOLE, worst=WORST):
         failed.append("worst position %.3g > %.2f x %.3g" % (pk, worst, pm))
     assert not failed, "%s: %s" % (name, "; ".join(failed))
     return wk, wm, wk / wm, pk, pm, pk / pm
+
+
+# ---- a second correct fp32 transform and its tables, for the CPU tests that prove the gate discriminates ----
+def table_exact(N):
+    """W_N^k, k < N/2, formed in double and rounded once."""
+    return np.exp(-2j * np.pi * np.arange(N // 2) / N).astype(np.complex64)
+
+
+def table_one_entry_off(N):
+    """... with one entry that only the last stage reads (an odd k) times 1 + 1e-6."""
+    t = table_exact(N)
+    k = N // 8 + 1
+    t[k] = np.complex64(np.complex128(t[k]) * (1.0 + 1e-6))
+    return t
+
+
+def table_fp32_angles(N):
+    """... with the angle -2 pi k / N formed in fp32."""
+    a = np.float32(-2.0 * np.pi) * np.arange(N // 2, dtype=np.float32) / np.float32(N)
+    assert a.dtype == np.float32
+    return (np.cos(a.astype(np.float64)) + 1j * np.sin(a.astype(np.float64))).astype(np.complex64)
+
+
+def fft_r2(x, table, inverse=False):
+    """Radix-2 decimation-in-time FFT of the rows of x in complex64 (unnormalised both ways); table:
+    W_N^k for k < N/2."""
+    F, N = x.shape
+    assert table.dtype == np.complex64 and table.size == N // 2
+    w = np.conj(table) if inverse else table
+    nb = N.bit_length() - 1
+    rev = np.zeros(N, np.int64)
+    for b in range(nb):
+        rev |= ((np.arange(N) >> b) & 1) << (nb - 1 - b)
+    a = np.ascontiguousarray(x, np.complex64)[:, rev]
+    m = 1
+    while m < N:
+        a = a.reshape(F, N // (2 * m), 2, m)
+        t = a[:, :, 1, :] * w[::N // (2 * m)][None, None, :]
+        a = np.stack([a[:, :, 0, :] + t, a[:, :, 0, :] - t], axis=2)
+        assert a.dtype == np.complex64
+        m *= 2
+    return a.reshape(F, N)

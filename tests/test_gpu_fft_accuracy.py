@@ -16,8 +16,8 @@ Models (complex64, on the same frames) and references (float64 on the same fp32 
                    the same in complex128.
   overlap-save     fft_xlat_ref.model_c64 and ref64; fft_filter_ccc is D = 1, inc = 0.
 
-The CPU tests (not marked gpu) prove that the gate discriminates: a radix-2 complex64 FFT written
-here, given its twiddle table, passes against the scipy model with the correctly rounded table, fails
+The CPU tests (not marked gpu) prove that the gate discriminates: a radix-2 complex64 FFT
+(fft_accuracy.fft_r2), given its twiddle table, passes against the scipy model with the correctly rounded table, fails
 the worst-position gate with one entry times 1 + 1e-6 and fails both gates with angles formed in fp32;
 the overlap-save chain built from it behaves the same with the table of its N/D-point inverse.
 
@@ -44,6 +44,7 @@ import pytest
 
 from tests import fft_accuracy as acc
 from tests import fft_xlat_ref as ref
+from tests.fft_accuracy import fft_r2, table_exact, table_fp32_angles, table_one_entry_off
 from tests.gpu_util import dev, hann, uniform
 
 gpu = pytest.mark.gpu
@@ -98,47 +99,6 @@ def chan_ref(x, w):
 
 
 # ---- CPU: the gate tells a correct fp32 transform from a subtly wrong one -------------------------
-def table_exact(N):
-    """W_N^k, k < N/2, formed in double and rounded once."""
-    return np.exp(-2j * np.pi * np.arange(N // 2) / N).astype(np.complex64)
-
-
-def table_one_entry_off(N):
-    """... with one entry that only the last stage reads (an odd k) times 1 + 1e-6."""
-    t = table_exact(N)
-    k = N // 8 + 1
-    t[k] = np.complex64(np.complex128(t[k]) * (1.0 + 1e-6))
-    return t
-
-
-def table_fp32_angles(N):
-    """... with the angle -2 pi k / N formed in fp32."""
-    a = np.float32(-2.0 * np.pi) * np.arange(N // 2, dtype=np.float32) / np.float32(N)
-    assert a.dtype == np.float32
-    return (np.cos(a.astype(np.float64)) + 1j * np.sin(a.astype(np.float64))).astype(np.complex64)
-
-
-def fft_r2(x, table, inverse=False):
-    """Radix-2 decimation-in-time FFT of the rows of x in complex64 (unnormalised both ways); table:
-    W_N^k for k < N/2."""
-    F, N = x.shape
-    assert table.dtype == np.complex64 and table.size == N // 2
-    w = np.conj(table) if inverse else table
-    nb = N.bit_length() - 1
-    rev = np.zeros(N, np.int64)
-    for b in range(nb):
-        rev |= ((np.arange(N) >> b) & 1) << (nb - 1 - b)
-    a = np.ascontiguousarray(x, np.complex64)[:, rev]
-    m = 1
-    while m < N:
-        a = a.reshape(F, N // (2 * m), 2, m)
-        t = a[:, :, 1, :] * w[::N // (2 * m)][None, None, :]
-        a = np.stack([a[:, :, 0, :] + t, a[:, :, 0, :] - t], axis=2)
-        assert a.dtype == np.complex64
-        m *= 2
-    return a.reshape(F, N)
-
-
 _cpu = {}
 
 

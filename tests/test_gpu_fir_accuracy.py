@@ -14,9 +14,8 @@ family on the models themselves), except the ones listed in fir_accuracy.py as n
 Part 3 (test_*split_alone*): one and two taps through FirPlan(MFMA), where the split is the only
 error, against the per-element bound of nsh_fir_mfma_shared.hpp's own statement (fir_accuracy.split_bound).
 
-Left out: nsh_fir_cascade_ccf (overlap-save on the composite filter). tests/test_gpu_pfft.py and
-test_gpu_pfft_taps.py hold it to a derived bound and print error-to-bound ratios; they have no fp32
-model of the chain to gate against.
+nsh_fir_cascade_ccf (overlap-save on the composite filter) has the same gate against a complex64 model
+of its chain in tests/test_gpu_pfft_accuracy.py.
 k_pfb<64> and k_pfb_synth<64> take at most 1024 taps (16 per branch), so their case is L = 1024, not 32 M.
 Neither FirPlan nor the library tells a caller which chunks went to the exact forms; the split-alone
 cases assert plan.kernel and restate chunk_needs_exact on the inputs (no chunk qualifies).

@@ -31,41 +31,17 @@ import functools
 
 import numpy as np
 import pytest
-import scipy.signal as ss
 
 from oracle import oracle as orc
 from newsched_amd import nsh
-from tests.pfft_ref import C5, KERNEL16, heq_l1, heq_of, pfft_form, ref_chain, run_pfft  # noqa: F401  (pfft_form: autouse)
+from tests.pfft_ref import (CHAINS_A, CHAINS_B, KERNEL16, M, geometry, heq_l1, launch_shape, many_frames_n_out, n_cu_of,  # noqa: F401
+                            pfft_form, ref64, ref_chain, run_pfft, taps_u)  # (pfft_form: autouse)
 
 gpu = pytest.mark.gpu
-M, IMG2, MAX_STAGES = 512, 571, 8
+IMG2, MAX_STAGES = 571, 8
 
 
 # ---------------------------------------------------------------- taps, composite, reference
-
-def taps_u(n, seed, scale=1.0):
-    """n taps, magnitudes uniform in [0.5, 1] * scale (a power of two), random signs."""
-    rng = np.random.default_rng(seed)
-    return (rng.uniform(0.5, 1.0, n) * rng.choice([-1.0, 1.0], n) * scale).astype(np.float32)
-
-
-def geometry(stages):
-    heq = heq_of(stages)
-    D = int(np.prod([d for _, d in stages]))
-    Q = (heq.size - 1 + D - 1) // D
-    return heq, D, Q, M - Q
-
-
-def ref64(x, heq, D, n_out, hist=None):
-    """y[m] = sum_n heq[n] s[m D - n] in float64, s = x preceded by hist (zeros before it)."""
-    s = np.asarray(x, np.complex128)
-    off = 0
-    if hist is not None and len(hist):
-        s = np.concatenate([np.asarray(hist, np.complex128), s])
-        off = len(hist)
-    full = ss.oaconvolve(s, np.asarray(heq, np.float64)) if s.size > 4 * heq.size else np.convolve(s, heq)
-    return full[off:off + D * n_out:D][:n_out]
-
 
 def plan_runs_stages(stages):
     """nsh_fir_cascade_plan_create's rule: inf/NaN frames run the stages when there are 2 .. 8 of them
@@ -130,18 +106,6 @@ def assert_pattern(y, r, what):
                                       err_msg="%s: inf signs (%s)" % (what, part))
 
 
-def launch_shape(n_out, V, D, n_cu):
-    """(frames, frames per workgroup, workgroups) as nsh_fir_cascade_ccf launches them."""
-    nf = (n_out + V - 1) // V
-    wg = min(nf, n_cu * (1 if D == 16 else 2))
-    fpw = (nf + wg - 1) // wg
-    return nf, fpw, (nf + fpw - 1) // fpw
-
-
-def n_cu_of(torch):
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
 def report(what, ratio):
     print("pfft_taps ratio %-44s %.4f" % (what, ratio))
 
@@ -177,22 +141,6 @@ def test_ref64_matches_oracle_chain():
 
 
 # ---------------------------------------------------------------- group A: taps
-
-def _single(L, D, seed=None):
-    return [(taps_u(L, 1000 + L if seed is None else seed), D)]
-
-
-CHAINS_A = {
-    "d16-L1": _single(1, 16), "d16-L2": _single(2, 16),
-    "d16-L17-q1": _single(17, 16), "d16-L33-q2": _single(33, 16),
-    "d16-L641-r0": _single(641, 16), "d16-L642-r1": _single(642, 16), "d16-L656-r15": _single(656, 16),
-    "d16-L4070-q255": _single(4070, 16), "d16-L4082-q256": _single(4082, 16), "d16-L4097-q256": _single(4097, 16),
-    "d8-L2": _single(2, 8), "d8-L2042-q256": _single(2042, 8), "d8-L2049-q256": _single(2049, 8),
-    "d16-2x8": [(taps_u(2, 21), 2), (taps_u(1000, 22), 8)],
-    "d16-4x2x2": [(taps_u(4, 31), 4), (taps_u(2, 32), 2), (taps_u(300, 33), 2)],
-    "d8-2x4": [(taps_u(2, 41), 2), (taps_u(700, 42), 4)],
-}
-
 
 @functools.lru_cache(maxsize=None)
 def _case_a(name):
@@ -324,22 +272,7 @@ def test_firplan_asymmetric_taps(torch_cuda, decim, ntaps, algo, pfft_form):
 # (frame maximum >= 2^124, < 2^-100)
 EXPONENTS = (0, 60, -60, 125, -110, 0)
 
-CHAINS_B = {
-    # the longest filters (V = 256); taps * 2^-12 so that |x| sum|heq| stays inside fp32 at 2^125
-    "d16-L4097": [(taps_u(4097, 5097, 2.0 ** -12), 16)],
-    "d8-L2049": [(taps_u(2049, 3049, 2.0 ** -11), 8)],
-    "c5": C5,
-    # Q = 192: V - Q = 128 rows of each frame lie in no other frame's window
-    "d16-L3073": [(taps_u(3073, 4073), 16)],
-    "d16-2x8-q192": [(taps_u(2, 51), 2), (taps_u(1536, 52), 8)],
-    "d8-L1537": [(taps_u(1537, 2537), 8)],
-    "d8-2x4-q192": [(taps_u(2, 61), 2), (taps_u(768, 62), 4)],
-}
 MIN_FPW = {16: 4, 8: 3}
-
-
-def many_frames_n_out(V, D, n_cu):
-    return (3 * n_cu if D == 16 else 2 * 2 * n_cu) * V + 1
 
 
 def assert_many_frames(n_out, V, D, n_cu):
