@@ -95,14 +95,28 @@ public:
     {
         add_tag(tag_t(offset, std::move(key), std::move(value), std::move(srcid)));
     }
-    // Copy tags of `in` that fall in the window this block is about to write.
-    void propagate_tags(std::shared_ptr<buffer> in, int n_consumed)
+    // Copy the tags on the n_consumed items a work() call read from `in` onto the n_produced
+    // items it is about to write here; call it before post_read / post_write. A tag follows its
+    // item, not the absolute count: with R = in's total_read() and W = this buffer's
+    // total_written(), a tag at R + k lands on W + floor(k * n_produced / n_consumed), in integer
+    // arithmetic (no relative_rate() double), or on W, the next item to be written, when the call
+    // produced nothing. For a fixed I:D block R and W advance by multiples of D and I, so the
+    // result, W0 + floor((t - R0) * I / D) from the counters (R0, W0) at the start of the run,
+    // does not depend on how the stream is cut into calls; a 1:M block puts the tag on the first
+    // of its M outputs. The block's group delay is not compensated.
+    void propagate_tags(std::shared_ptr<buffer> in, int n_consumed, int n_produced)
     {
-        if (auto* t = tag_target(); t != this) return t->propagate_tags(std::move(in), n_consumed);
+        if (auto* t = tag_target(); t != this) return t->propagate_tags(std::move(in), n_consumed, n_produced);
+        if (n_consumed <= 0) return;
+        const uint64_t first = in->total_read(), c = (uint64_t)n_consumed, p = (uint64_t)std::max(n_produced, 0);
         std::vector<tag_t> src = in->tags();
         std::lock_guard<std::mutex> g(_buf_mutex);
         for (auto& t : src)
-            if (t.offset >= _total_written && t.offset < _total_written + (uint64_t)n_consumed) _tags.push_back(t);
+            if (t.offset >= first && t.offset < first + c) {
+                tag_t moved = t;
+                moved.offset = _total_written + (t.offset - first) * p / c; // p == 0: the next item to be written
+                _tags.push_back(std::move(moved));
+            }
     }
     void prune_tags(int n_consumed)
     {

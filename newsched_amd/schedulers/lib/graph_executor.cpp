@@ -200,7 +200,8 @@ std::map<nodeid_t, executor_iteration_status> graph_executor::run_one_iteration(
                 for (size_t o = 0; o < out_ports.size(); ++o)
                     if (pol == tag_propagation_policy_t::TPP_ALL_TO_ALL ||
                         (pol == tag_propagation_policy_t::TPP_ONE_TO_ONE && o == i))
-                        for (auto& ob : _bufman->get_output_buffers(out_ports[o])) ob->propagate_tags(buf, consumed);
+                        for (auto& ob : _bufman->get_output_buffers(out_ports[o]))
+                            ob->propagate_tags(buf, consumed, wout[o].n_produced);
                 buf->prune_tags(consumed);
             }
             if (consumed > 0) {

@@ -46,6 +46,22 @@ def test_tags_through_device_edges():
     assert "2 test(s), 0 failure(s)" in out
 
 
+def test_tags_through_rate_changing_blocks():
+    """A tag follows its item through every CPU block with relative_rate() != 1: the complete list
+    of (sequence number, offset) pairs against the closed form floor(t I / D), with many and with
+    few work() calls, tag policies, fan-out, a domain boundary and a restart."""
+    out = run("qa_tags", 300, "HostRateTags")
+    assert "21 test(s), 0 failure(s)" in out
+
+
+@pytest.mark.gpu
+def test_tags_through_rate_changing_hip_blocks():
+    """The same through every rate-changing gr::hip block over H2D / D2H edges, and through the
+    fused and the staged FIR cascade in a scheduler_hip domain."""
+    out = run("qa_tags", 300, "DeviceRateTags")
+    assert "12 test(s), 0 failure(s)" in out
+
+
 def test_fusion_pass_graph_rewrite():
     """scheduler_hip's fusion passes (elementwise chains, fft -> w -> ifft channelizer) as host
     logic (no device touched)."""
